@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the Tuner -> WBFM hot path on MI355X (BASELINE.json config 4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One step = one pass of the hot path over one 1-second wideband buffer that is
 already resident in HBM: Tuner.load (FFT of N = 240 000 000 complex64 samples)
@@ -24,6 +24,9 @@ the diagnosis in `rotating`).  Before them rank 0 times the same K steps alone
 must reproduce bit for bit (`self_check`).
 N = 1 allocates --placement-sets complete handle sets and reports the median
 one (`placement_spread` = fastest and slowest set).
+
+--dump-outputs DIR writes the audio of the last timed step (a fixed seeded sample of channels when it is
+larger than DUMP_BYTES) as .npy files, for comparing the outputs of two builds on identical inputs.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying
 `roofline` (dominant stage, algorithmic bytes per launch / HIP-event time per
@@ -104,6 +107,20 @@ def path_read_bytes(N, C, B, A, kind):
     return 8.0 * N + C * (8.0 * B + per_ch)
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: at most this much audio per run
+
+
+def dump_sample(audio):
+    """What --dump-outputs writes of a [channels, A, ch] audio block: every channel when the block fits DUMP_BYTES,
+    else a fixed seeded sample of channels, the same in every run and every build, so that two builds can be compared
+    output for output.  `audio_channels` holds the channel index of each row."""
+    C = audio.shape[0]
+    keep = min(C, DUMP_BYTES // (audio[0].numel() * audio.element_size()))
+    idx = np.arange(C) if keep == C else np.sort(np.random.default_rng(0).choice(C, keep, replace=False))
+    return {"audio": audio[torch.as_tensor(idx, device=audio.device)].cpu().numpy(),
+            "audio_channels": idx.astype(np.float64)}
+
+
 def dist_env():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -155,15 +172,22 @@ def host_memory_gb():
     return None
 
 
+# The workers of the parallel CPU baseline are forks of this process and inherit its open GPU device files, so each
+# one counts as a process holding the GPU; a shared node allows few of those at once.  `cpu_baseline.fair` is therefore
+# at most a 4-core figure (its `cores` field says how many): it understates a large host, and GPU-vs-CPU ratios taken
+# from it are ratios against those cores, not against the whole host.
+FORK_WORKERS_MAX = 4
+
+
 def fair_workers(requested, per_worker_gb=10.0):
     """Worker processes of the parallel CPU baseline: half the logical cores (one per physical core of an SMT-2
     host), capped by memory -- each worker rolls and windows the whole N-point spectrum like the reference
-    (~8 GB live at N = 2.4e8) -- unless --cpu-workers asks for a number."""
+    (~8 GB live at N = 2.4e8) -- unless --cpu-workers asks for a number; never more than FORK_WORKERS_MAX."""
     if requested > 0:
-        return requested
+        return min(requested, FORK_WORKERS_MAX)
     cores = max(1, (os.cpu_count() or 2) // 2)
     mem = host_memory_gb()
-    return max(1, min(cores, int(mem // per_worker_gb))) if mem else min(cores, 8)
+    return min(FORK_WORKERS_MAX, max(1, min(cores, int(mem // per_worker_gb))) if mem else min(cores, 8))
 
 
 def cpu_baseline(x_host, f_in, centres, N, C, B, A, kind, nchan, workers):
@@ -214,8 +238,8 @@ def cpu_baseline(x_host, f_in, centres, N, C, B, A, kind, nchan, workers):
             t_fair = t_load + C / rate
             info["fair"] = {
                 "value": N / t_fair / 1e6, "unit": "Msamples/s", "cores": workers,
-                "pool": "min(logical cores // 2 = %d, MemAvailable // 10 GB = %s)" % (
-                    max(1, (os.cpu_count() or 2) // 2), int((host_memory_gb() or 0) // 10)),
+                "pool": "min(logical cores // 2 = %d, MemAvailable // 10 GB = %s, %d forked workers)" % (
+                    max(1, (os.cpu_count() or 2) // 2), int((host_memory_gb() or 0) // 10), FORK_WORKERS_MAX),
                 "sample": "same load + %d channel runs on %d worker processes in %.1f s (%.2f channels/s), "
                           "extrapolated t_load + C/rate = %.0f s per buffer" % (len(todo), workers, wall, rate, t_fair),
             }
@@ -378,7 +402,7 @@ def measure_config(name, lib, hip, steps, warmup, chunk=0, with_surface=True):
     rcfm_tuner_load + rcfm_pipeline_run, input resident in HBM, same accounting as the headline."""
     N, C, B, A, raster, kind = CONFIGS[name]
     ch = 2 if kind == "WBFM" else 1
-    x, centres, f_in = synth_wideband_on_device(N, C, B, raster, kind, lib, hip)
+    x, centres, f_in = synth_wideband_on_device(N, C, B, raster, kind)
     rolls = (ctypes.c_int64 * C)(*[int(f_in - f) for f in centres])
     bws = (ctypes.c_int32 * C)(*([B] * C))
     tuner, demod = ctypes.c_void_p(), ctypes.c_void_p()
@@ -438,7 +462,7 @@ def measure_path_map(lib, hip, steps=10, warmup=2, C=64, N=16_000_000):
     cells = {}
     for B in PATH_MAP_B:
         raster = N // (C + 2)
-        x, centres, f_in = synth_wideband_on_device(N, C, B, raster, "WBFM", lib, hip)
+        x, centres, f_in = synth_wideband_on_device(N, C, B, raster, "WBFM")
         rolls = (ctypes.c_int64 * C)(*[int(f_in - f) for f in centres])
         bws = (ctypes.c_int32 * C)(*([B] * C))
         tuner = ctypes.c_void_p()
@@ -611,7 +635,7 @@ def parse_args():
     ap.add_argument("--cpu-workers", type=int, default=0,
                     help="worker processes of the parallel ('fair') CPU baseline; 0 = size the pool from the host: "
                          "min(logical cores // 2, MemAvailable // 10 GB) -- each worker holds ~8 GB while it rolls "
-                         "and windows the 240M-point spectrum; 1 = skip")
+                         "and windows the 240M-point spectrum; 1 = skip; at most %d" % FORK_WORKERS_MAX)
     ap.add_argument("--parallelism", default="both", choices=["both", "replicated", "rotating"],
                     help="N > 1: 'replicated' = every rank runs the whole wideband FFT and its own channels; 'rotating' = "
                          "rank i mod N owns buffer i (ingest + FFT) and sends each peer the spectrum bins its channels "
@@ -637,6 +661,11 @@ def parse_args():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the other GPU configurations (cfg3, cfg5, batched cfg2) reported beside the headline")
     ap.add_argument("--profile-all", action="store_true", help="print the per-stage table to stderr as well")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last timed step -- the audio a caller receives (N > 1: "
+                         "rank 0's gathered block) -- to DIR/audio.npy (float32, [channels, A, ch]; a fixed seeded sample "
+                         "of %d MB when the block is larger) and the channel of each row to DIR/audio_channels.npy "
+                         "(float64)" % (DUMP_BYTES >> 20))
     ap.add_argument("--no-pcie", action="store_true",
                     help="skip the host-fed pass (page-locked host buffer, H2D of buffer i+1 on a copy stream overlapped "
                          "with the kernels of buffer i: extra field pcie_inclusive, never `value`)")
@@ -662,9 +691,11 @@ def die(what, code=2, **more):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher (how the driver starts N = 1): become
+    """`python bench.py --gpus N` without a launcher (how the driver starts N = 1): run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py
-    <the same arguments>` -- one process per GPU, rank 0 prints the one line."""
+    <the same arguments>` -- one process per GPU, rank 0 prints the one line -- and leave with its status.  A child
+    process, not exec: counting the devices may already have initialised the GPU runtime in this process."""
+    import subprocess
     have = torch.cuda.device_count()
     if "RCFM_BENCH_DEVICE" not in os.environ and have < args.gpus:
         die("bench.py --gpus %d: this node shows %d GPU(s)" % (args.gpus, have), gpus=args.gpus, visible=have)
@@ -674,7 +705,8 @@ def self_launch(args):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)          # a launcher killed by a signal: the shell's 128 + signal
 
 
 class Run:
@@ -935,6 +967,11 @@ def measure_partitioning(run, x, centres, f_in, parallelism, primary, ref=None):
         dt = time.perf_counter() - t0
         timed.append((dt, read_profile(lib)[dominant], hs))
         lib.rcfm_profile_enable(ctypes.c_uint64(0))
+    if primary and rank == 0 and args.dump_outputs:
+        # the last timed step was the last set's: its audio block (row i = channel i at N = 1), or the gathered block
+        slot = (counter[0] - 1) % nbuf
+        for name, a in dump_sample(gathereds[slot] if multi else cur["set"]["audios"][slot]).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     order = sorted(range(len(timed)), key=lambda i: timed[i][0])
     pick = order[len(order) // 2]                 # 4 sets: the third fastest (the upper median)
     elapsed, dom, median_set = timed[pick]
@@ -1307,8 +1344,12 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         die("--gpus must be at least 1")
+    if args.steps < 1:
+        die("--steps must be at least 1")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)                      # does not return
+        self_launch(args)                      # does not return: exits with the launcher's status
     run = Run(args)
     if run.world != args.gpus:
         # a launcher's world that is not what --gpus asked for is a mis-launch, whichever way round: refuse it rather
@@ -1325,7 +1366,7 @@ def main():
     hip.torch()
 
     N, C, B, A, raster, kind = CONFIGS[args.config]
-    x, centres, f_in = synth_wideband_on_device(N, C, B, raster, kind, lib, hip)
+    x, centres, f_in = synth_wideband_on_device(N, C, B, raster, kind)
 
     legs = ["replicated", "rotating"] if (args.parallelism == "both" and run.world > 1) else \
            ["replicated" if args.parallelism == "both" else args.parallelism]

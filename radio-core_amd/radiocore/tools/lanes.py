@@ -111,7 +111,13 @@ class Lanes:
         storage stream-ordered (``with feeder.next() as x: t = lanes.submit(x); lanes.hold_current_stream(t)`` -- the
         Feeder frees the slot behind the current stream, which must therefore wait for the lane that still reads it).
         It does NOT wait for the buffer's audio: the next submit() waits for the current stream, and a wait for the
-        whole buffer there would run the lanes one after the other."""
+        whole buffer there would run the lanes one after the other.
+        Caveat: streams share in-order hardware queues when the runtime has fewer queues than streams (GPU_MAX_HW_QUEUES;
+        with 2, the default stream shares one with a lane).  The current stream's wait then lasts until everything
+        queued before it on that queue has run -- the lane's whole buffer -- and the lanes serialise.  On such a runtime,
+        run the recipe from a stream that gets a queue of its own, e.g. ``torch.cuda.Stream(priority=-1)`` (each
+        priority has its own queues) made current in a process whose streams do not already fill that priority's
+        queues (tests/test_hip_lanes.py)."""
         self._torch.cuda.current_stream().wait_event(self._pending[ticket][2])
 
     def drain(self):

@@ -62,7 +62,8 @@ def test_two_rank_dry_run_prints_one_contract_line(parallelism):
     assert g["finite"] and g["own_block_equal"] and g["blocks_with_audio"] == g["blocks"] == 2
     # the same launch timed ONE rank first (rank 0 alone) and kept its audio: this partitioning reproduced it bit for bit
     assert r["n1"]["value"] > 0 and r["n1"]["steps"] == 3
-    assert abs(r["speedup_vs_n1"] - r["value"] / r["n1"]["value"]) <= 1e-3 * r["speedup_vs_n1"]
+    # speedup_vs_n1 is rounded to 4 decimals: at the small speed-ups of a dry run that rounding alone exceeds 1e-3
+    assert abs(r["speedup_vs_n1"] - r["value"] / r["n1"]["value"]) <= 1e-3 * r["speedup_vs_n1"] + 5e-5
     sc = r["self_check"]
     assert sc["bit_identical"] is True and sc["max_abs_diff"] == 0.0 and sc["peak"] > 1e-3 and sc["channels"] == r["config"]["channels"]
     assert "partitionings" not in r                                  # one leg: nothing to choose between
@@ -131,7 +132,7 @@ def test_plain_python_launch_starts_its_own_ranks_and_reports_both_partitionings
         assert leg["gather_check"]["finite"] and leg["gather_check"]["blocks_with_audio"] == 2
         assert leg["self_check"]["bit_identical"] is True            # one buffer through each: the single-GPU audio
     # one GPU in the same launch, and the published speed-up against it
-    assert r["n1"]["value"] > 0 and abs(r["speedup_vs_n1"] - r["value"] / r["n1"]["value"]) <= 1e-3 * r["speedup_vs_n1"]
+    assert r["n1"]["value"] > 0 and abs(r["speedup_vs_n1"] - r["value"] / r["n1"]["value"]) <= 1e-3 * r["speedup_vs_n1"] + 5e-5
     assert r["rccl_ranks"] == 0 and r["cpu_baseline"] is None
 
 

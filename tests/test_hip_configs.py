@@ -179,7 +179,7 @@ def _full_config(rc, oracle, name, sample, buffers=1):
     from radiocore._internal import hip
     N, C, B, A, raster, kind = bench.CONFIGS[name]
     lib = hip.lib()
-    x, centres, f_in = workloads_device.synth_wideband_on_device(N, C, B, raster, kind, lib, hip)
+    x, centres, f_in = workloads_device.synth_wideband_on_device(N, C, B, raster, kind)
     tuner = rc.Tuner()
     for f in centres:
         tuner.add_channel(f, B, getattr(rc, kind)(B, A))
@@ -577,7 +577,7 @@ def test_cfg4_shards_reproduce_the_whole_band_bit_for_bit_under_both_wideband_pl
     from radiocore._internal import hip
     lib = hip.lib()
     N, C, B, A, raster, kind = bench.CONFIGS["cfg4"]
-    x, centres, f_in = workloads_device.synth_wideband_on_device(N, C, B, raster, kind, lib, hip)
+    x, centres, f_in = workloads_device.synth_wideband_on_device(N, C, B, raster, kind)
     rolls = (ctypes.c_int64 * C)(*[int(f_in - f) for f in centres])
     bws = (ctypes.c_int32 * C)(*([B] * C))
     s = hip.stream()

@@ -15,7 +15,6 @@
     recorded in INTEGRATION.md.
 """
 
-import multiprocessing as mp
 import os
 
 import numpy as np
@@ -23,6 +22,7 @@ import pytest
 
 import workloads
 from conftest import TOL, have_gpu, rel_err
+from oracle_pool import oracle_audio
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not have_gpu(), reason="needs an MI355X")]
 
@@ -42,31 +42,11 @@ def oracle():
     return radiocore_oracle
 
 
-def _demod_worker(args):
-    """Runs in a spawned process (no GPU context): the oracle's demodulator on one channel's IQ, two buffers."""
-    kind, B, A, iqs = args
-    import radiocore_oracle as oracle
-    d = getattr(oracle, kind)(B, A)
-    ch = 2 if kind == "WBFM" else 1
-    return [np.asarray(d.run(iq)).reshape(A, ch).astype(np.float32) for iq in iqs]
-
-
-def _oracle_audio(kind, B, A, iq_per_channel):
-    """{channel: [audio per buffer]} through a pool of oracle workers."""
-    items = sorted(iq_per_channel.items())
-    workers = max(1, min(32, (os.cpu_count() or 2) // 2, len(items)))
-    ctx = mp.get_context("spawn")
-    with ctx.Pool(workers) as pool:
-        res = pool.map(_demod_worker, [(kind, B, A, iqs) for _, iqs in items], chunksize=1)
-    return {c: r for (c, _), r in zip(items, res)}
-
-
 def _setup(rc, name):
     import bench
     import workloads_device
-    from radiocore._internal import hip
     N, C, B, A, raster, kind = bench.CONFIGS[name]
-    x, centres, f_in = workloads_device.synth_wideband_on_device(N, C, B, raster, kind, hip.lib(), hip)
+    x, centres, f_in = workloads_device.synth_wideband_on_device(N, C, B, raster, kind)
     return N, C, B, A, kind, x, centres, f_in
 
 
@@ -131,7 +111,7 @@ def _sampled_vs_oracle(rc, oracle, name, sample, buffers):
         ref.load(x_host)
         for i in sample:
             iqs[i].append(np.asarray(ref.run_pruned(i)))
-    want = _oracle_audio(kind, B, A, iqs)
+    want = oracle_audio(kind, B, A, iqs)
     errs = {}
     for j, i in enumerate(sample):
         errs[i] = max(rel_err(got[buf][j], want[i][buf]) for buf in range(buffers))

@@ -34,7 +34,6 @@ def main():
     ap.add_argument("libs", nargs="+", help="name=path")
     args = ap.parse_args()
     hip.torch()
-    base = hip.lib()
     libs = []
     for item in args.libs:
         name, _, path = item.partition("=")
@@ -49,7 +48,7 @@ def main():
         topts.setdefault(name, []).append(rest)
     N, C, B, A, raster, kind = bench.CONFIGS[args.config]
     ch = 2 if kind == "WBFM" else 1
-    x, centres, f_in = bench.synth_wideband_on_device(N, C, B, raster, kind, base, hip)
+    x, centres, f_in = bench.synth_wideband_on_device(N, C, B, raster, kind)
     rolls = (ctypes.c_int64 * C)(*[int(f_in - f) for f in centres])
     bws = (ctypes.c_int32 * C)(*([B] * C))
     chunk_ch = min(8192, max(1024, 1024 * 240000 // B))

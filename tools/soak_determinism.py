@@ -21,7 +21,7 @@ def main(reps=100, config="cfg4"):
     hip.torch()
     N, C, B, A, raster, kind = bench.CONFIGS[config]
     ch = 2 if kind == "WBFM" else 1
-    x, centres, f_in = synth_wideband_on_device(N, C, B, raster, kind, lib, hip)
+    x, centres, f_in = synth_wideband_on_device(N, C, B, raster, kind)
     rolls = (ctypes.c_int64 * C)(*[int(f_in - f) for f in centres])
     bws = (ctypes.c_int32 * C)(*([B] * C))
     tuner, demod = ctypes.c_void_p(), ctypes.c_void_p()

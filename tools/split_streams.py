@@ -21,7 +21,7 @@ def main(config="cfg3", parts=2, steps=40):
     N, C, B, A, raster, kind = bench.CONFIGS[config]
     ch = 2 if kind == "WBFM" else 1
     kid = {"FM": 0, "MFM": 1, "WBFM": 2}[kind]
-    x, centres, f_in = bench.synth_wideband_on_device(N, C, B, raster, kind, lib, hip)
+    x, centres, f_in = bench.synth_wideband_on_device(N, C, B, raster, kind)
     rolls = (ctypes.c_int64 * C)(*[int(f_in - f) for f in centres])
     bws = (ctypes.c_int32 * C)(*([B] * C))
     tuners, demods, streams = [], [], []

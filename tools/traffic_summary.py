@@ -86,8 +86,9 @@ def main():
                 e["read_bytes"] += rd
                 e["written_bytes"] += wr
                 break
-    # the input synthesis of bench.py runs the wideband FFT once with the plain last-pass store; the bench itself
-    # (rcfm_tuner_shard) uses the row-window store: keep the latter
+    # a trace may hold the wideband FFT with the plain last-pass store as well (a tuner without a shard; traces taken
+    # while bench.py still built its input with the library); the bench itself (rcfm_tuner_shard) uses the row-window
+    # store: keep the latter
     fft = stages.get("tuner_fft_N")
     if fft and any("StoreRowWindow" in k["kernel"] for k in fft["kernels"]):
         windowed = {k["kernel"].split(", Store")[0] for k in fft["kernels"] if "StoreRowWindow" in k["kernel"]}

@@ -20,7 +20,7 @@ def main(nstreams, steps=20, config="cfg4"):
     hip.torch()
     N, C, B, A, raster, kind = bench.CONFIGS[config]
     ch = 2 if kind == "WBFM" else 1
-    x, centres, f_in = bench.synth_wideband_on_device(N, C, B, raster, kind, lib, hip)
+    x, centres, f_in = bench.synth_wideband_on_device(N, C, B, raster, kind)
     rolls = [int(f_in - f) for f in centres]
     roll_a = (ctypes.c_int64 * C)(*rolls)
     bw_a = (ctypes.c_int32 * C)(*([B] * C))

@@ -1,17 +1,16 @@
 """Seeded synthetic wideband buffers built ON the GPU (bench.py and the full-size -m gpu tests).
 
-Input generation is not the product: torch operators are used freely here, and the inverse
-wideband FFT borrows the library's own forward engine.  Same recipe as workloads.py (stations on
-the channel centres, integer-Hz tones, periodic in the 1-second buffer).
+Input generation is not the product: torch operators are used freely here, and only they: the
+buffer never passes through librcfm, so every build of the library is measured on the same input.
+Same recipe as workloads.py (stations on the channel centres, integer-Hz tones, periodic in the
+1-second buffer).
 """
-
-import ctypes
 
 import numpy as np
 import torch
 
 
-def synth_wideband_on_device(N, C, B, raster, kind, lib, hip):
+def synth_wideband_on_device(N, C, B, raster, kind):
     """Seeded synthetic wideband buffer built on the GPU (input generation is not the
     product: torch ops are used freely here).  Stations sit on the channel centres;
     each is an FM signal whose modulation is integer-Hz tones (+ 19 kHz pilot and a
@@ -47,20 +46,9 @@ def synth_wideband_on_device(N, C, B, raster, kind, lib, hip):
             off = int(centres[i] - f_in)
             Xw.index_add_(0, (kk + off) % N, S[j])
         del L, R, mpx, phase, s, S
-    # x = IFFT_N(Xw) = conj(FFT_N(conj(Xw))) / N, using the library's own wideband FFT
-    roll = (ctypes.c_int64 * 1)(0)
-    bw = (ctypes.c_int32 * 1)(min(B, N))
-    h = ctypes.c_void_p()
-    hip.check(lib.rcfm_tuner_create(N, 1, roll, bw, ctypes.byref(h)))
-    Xw = torch.conj_physical(Xw)
-    hip.check(lib.rcfm_tuner_load(h, hip.ptr(Xw), hip.stream()))
-    spec = ctypes.c_void_p()
-    hip.check(lib.rcfm_tuner_spectrum(h, ctypes.byref(spec)))
-    x = torch.empty(N, dtype=torch.complex64, device=dev)
-    hip.check(lib.rcfm_memcpy_d2d(hip.ptr(x), spec, N * 8, hip.stream()))
-    torch.cuda.synchronize()
-    hip.check(lib.rcfm_tuner_destroy(h))
-    x = torch.conj_physical(x) / N
+    # x = IFFT_N(Xw) by torch (rocFFT), not by the library under test: a build whose wideband FFT is wrong must not
+    # also change its own input (a conjugation error, for one, would cancel between the two transforms)
+    x = torch.fft.ifft(Xw)
     noise = torch.randn(N, 2, generator=torch.Generator(device=dev).manual_seed(7), device=dev) * 0.003
     x += torch.view_as_complex(noise)
     del Xw, noise
