@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the Tuner -> WBFM hot path on MI355X (BASELINE.json config 4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One step = one pass of the hot path over one 1-second wideband buffer that is
 already resident in HBM: Tuner.load (FFT of N = 240 000 000 complex64 samples)
@@ -19,9 +19,7 @@ BOTH partitionings of the wideband FFT back to back -- replicated, then the
 rotating owner -- and publishes the FASTER one whose gathered audio was verified
 as `value` (`config.parallelism` names it; the other keeps its own block,
 `rotating` or `replicated`; a failing second leg leaves the replicated line with
-the diagnosis in `rotating`).  Before them rank 0 times the same K steps alone
-(`n1`, `speedup_vs_n1`) and keeps one buffer's audio, which each partitioning
-must reproduce bit for bit (`self_check`).
+the diagnosis in `rotating`).
 N = 1 allocates --placement-sets complete handle sets and reports the median
 one (`placement_spread` = fastest and slowest set).
 
@@ -30,8 +28,16 @@ larger than DUMP_BYTES) as .npy files, for comparing the outputs of two builds o
 
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying
 `roofline` (dominant stage, algorithmic bytes per launch / HIP-event time per
-launch, against 8 TB/s) and, at N = 1, `cpu_baseline` (the numpy oracle timed on
-this box's host cores on a bounded sample: one load + a few channels).
+launch inside the timed region, against 8 TB/s).
+
+A plain run does only what that line's headline needs: set up, warm up, time the K steps, dump, print.  --full
+adds everything else, each outside the timed region:
+  - `stages` of the median handle set (N = 1: one fully bracketed step of its own);
+  - `pipelined` (two lanes over pairs of the handle sets) and `pcie_inclusive` (the host-fed loop);
+  - at N = 1, `cpu_baseline` (the numpy oracle timed on this box's host cores on a bounded sample: one load + a
+    few channels) and `parity_vs_oracle`; for cfg4, `other_configs` and `surface`;
+  - at N > 1, the one-rank leg on rank 0 (`n1`, `speedup_vs_n1`) whose audio each partitioning must reproduce
+    bit for bit (`self_check`), and the spectrum ring's own timing pass (`per_rank` sends and waits).
 """
 
 import argparse
@@ -631,11 +637,16 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg4", choices=sorted(CONFIGS))
     ap.add_argument("--chunk", type=int, default=0, help="channels per pass (0 = library default)")
-    ap.add_argument("--cpu-channels", type=int, default=8, help="channels in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well (module docstring): stages, lanes, "
+                         "host-fed loop, CPU baseline and oracle parity, other configurations, the N > 1 one-rank leg "
+                         "and self check; a plain run only times the headline")
+    ap.add_argument("--cpu-channels", type=int, default=8,
+                    help="--full: channels in the CPU baseline sample (0 = skip)")
     ap.add_argument("--cpu-workers", type=int, default=0,
-                    help="worker processes of the parallel ('fair') CPU baseline; 0 = size the pool from the host: "
-                         "min(logical cores // 2, MemAvailable // 10 GB) -- each worker holds ~8 GB while it rolls "
-                         "and windows the 240M-point spectrum; 1 = skip; at most %d" % FORK_WORKERS_MAX)
+                    help="--full: worker processes of the parallel ('fair') CPU baseline; 0 = size the pool from the "
+                         "host: min(logical cores // 2, MemAvailable // 10 GB) -- each worker holds ~8 GB while it "
+                         "rolls and windows the 240M-point spectrum; 1 = skip; at most %d" % FORK_WORKERS_MAX)
     ap.add_argument("--parallelism", default="both", choices=["both", "replicated", "rotating"],
                     help="N > 1: 'replicated' = every rank runs the whole wideband FFT and its own channels; 'rotating' = "
                          "rank i mod N owns buffer i (ingest + FFT) and sends each peer the spectrum bins its channels "
@@ -654,21 +665,24 @@ def parse_args():
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="rcfm_demod_set_option on every demodulator handle of the timed legs (A/B runs: tools/ab_args.sh): "
                          + ", ".join(sorted(DEMOD_OPTIONS)))
-    ap.add_argument("--self-check", action="store_true", help=argparse.SUPPRESS)     # the default for N > 1
+    ap.add_argument("--self-check", action="store_true",
+                    help="N > 1: the one-rank leg and `self_check` of --full without the rest of it")
     ap.add_argument("--no-self-check", action="store_true",
-                    help="N > 1: skip the one-rank leg on rank 0 (`n1`, `speedup_vs_n1`) and the bit-for-bit comparison of "
-                         "one buffer through each partitioning with the single-GPU audio (`self_check`)")
+                    help="N > 1, --full: skip the one-rank leg on rank 0 (`n1`, `speedup_vs_n1`) and the bit-for-bit "
+                         "comparison of one buffer through each partitioning with the single-GPU audio (`self_check`)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the other GPU configurations (cfg3, cfg5, batched cfg2) reported beside the headline")
-    ap.add_argument("--profile-all", action="store_true", help="print the per-stage table to stderr as well")
+                    help="--full: skip the two-lane pass and the other GPU configurations (cfg3, cfg5, batched cfg2, "
+                         "...) reported beside the headline")
+    ap.add_argument("--profile-all", action="store_true",
+                    help="print the per-stage table to stderr as well (and carry `stages` without --full)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the timed path computed in its last timed step -- the audio a caller receives (N > 1: "
                          "rank 0's gathered block) -- to DIR/audio.npy (float32, [channels, A, ch]; a fixed seeded sample "
                          "of %d MB when the block is larger) and the channel of each row to DIR/audio_channels.npy "
                          "(float64)" % (DUMP_BYTES >> 20))
     ap.add_argument("--no-pcie", action="store_true",
-                    help="skip the host-fed pass (page-locked host buffer, H2D of buffer i+1 on a copy stream overlapped "
-                         "with the kernels of buffer i: extra field pcie_inclusive, never `value`)")
+                    help="--full: skip the host-fed pass (page-locked host buffer, H2D of buffer i+1 on a copy stream "
+                         "overlapped with the kernels of buffer i: extra field pcie_inclusive, never `value`)")
     ap.add_argument("--pcie", action="store_true", help=argparse.SUPPRESS)     # rounds 1-4 spelling: now the default
     return ap.parse_args()
 
@@ -733,8 +747,8 @@ class Run:
         self.limit = float(os.environ.get("RCFM_BENCH_TIMEOUT", "300"))
         # the line of the legs that have finished: a later leg that fails still publishes them (rank 0)
         self.finished = None
-        # --self-check (default for N > 1): the one-rank leg + the bit-for-bit comparison of both partitionings with it
-        self.self_check = self.multi and not args.no_self_check
+        # --self-check (part of --full): the one-rank leg + the bit-for-bit comparison of both partitionings with it
+        self.self_check = self.multi and (args.full or args.self_check) and not args.no_self_check
 
     def progress(self, name, step=-1):
         self.phase.update(name=name, step=step, t=time.monotonic())
@@ -979,11 +993,12 @@ def measure_partitioning(run, x, centres, f_in, parallelism, primary, ref=None):
     cur["set"] = median_set
     tuner, demod = median_set["tuner"], median_set["demod"]
     audio = median_set["audios"][0]
-    if nsets > 1:                                 # the decomposition of the set the value comes from
-        prof_all = profile_pass(1)
+    stages_prof = prof_all                        # `stages`: one bracketed step of the set the value comes from
+    if nsets > 1:                                 # pass 1 ran on set 0: the median set needs a step of its own
+        stages_prof = profile_pass(1) if (args.full or args.profile_all) else None
 
     lanes_block = None
-    if primary and not multi and nsets >= 2 and not args.no_extras:
+    if args.full and primary and not multi and nsets >= 2 and not args.no_extras:
         progress("two lanes over pairs of the handle sets")
         lanes_block = measure_lane_pairs(lib, hip, x, sets, [t[0] / args.steps for t in timed], lo, mine, N, C, B, A, kind,
                                          args.steps, args.warmup)
@@ -1000,7 +1015,9 @@ def measure_partitioning(run, x, centres, f_in, parallelism, primary, ref=None):
         mine_ms = 1e3 * own_elapsed / args.steps
         row = {"rank": rank, "channels": mine, "step_ms": round(mine_ms, 4), "fft_ms": round(fft_pb, 4),
                "chan_ms": round(chan_pb, 4), "send_ms": 0.0, "wait_ms": 0.0}
-        if ring is not None:
+        if ring is not None and not args.full:
+            row.update(send_ms=None, wait_ms=None)               # the ring's timing pass is part of --full
+        elif ring is not None:
             progress("ring timing pass")
             ring.enable_timing()
             for _ in range(2 * world):
@@ -1010,7 +1027,8 @@ def measure_partitioning(run, x, centres, f_in, parallelism, primary, ref=None):
             ring.disable_timing()
             row.update(fft_ms=tsum.get("fft_ms", 0.0), send_ms=tsum.get("send_ms", 0.0), wait_ms=tsum.get("wait_ms", 0.0),
                        owned_buffers=tsum.get("fft_count", 0))
-        row["other_ms"] = round(mine_ms - row["chan_ms"] - row["wait_ms"] - (0.0 if rotating else row["fft_ms"]), 4)
+        row["other_ms"] = None if row["wait_ms"] is None else round(
+            mine_ms - row["chan_ms"] - row["wait_ms"] - (0.0 if rotating else row["fft_ms"]), 4)
         progress("per-rank rows")
         rows = [None] * world
         dist.all_gather_object(rows, row)
@@ -1075,9 +1093,10 @@ def measure_partitioning(run, x, centres, f_in, parallelism, primary, ref=None):
             "note": "a stage launch = the %d kernel launches named in `kernel`, bracketed by one HIP-event pair on their "
                     "stream inside the timed region; achieved = algorithmic_bytes_per_launch / launch_us" % len(launches),
         },
-        # one step of the set `value` comes from, every stage bracketed (untimed pass after the timed region)
-        "stages": stage_table(prof_all, N, B, A, kind, mine),
     }
+    if stages_prof is not None:
+        # one step of the set `value` comes from, every stage bracketed (untimed, outside the timed region)
+        result["stages"] = stage_table(stages_prof, N, B, A, kind, mine)
     if nsets > 1:
         per_set = [round(1e3 * t[0] / args.steps, 4) for t in timed]
         result["placement_spread"] = [min(per_set), max(per_set)]
@@ -1155,7 +1174,7 @@ def measure_partitioning(run, x, centres, f_in, parallelism, primary, ref=None):
                     "peak": peak, "channels": C,
                     "against": "one buffer from first-buffer state on ONE GPU (rank 0, same launch), all %d channels" % C}
 
-    if not args.no_pcie:
+    if args.full and not args.no_pcie:
         # Host-fed variant (DESIGN.md sections 4, 5): the wideband buffer starts in page-locked host memory
         # (radiocore.tools.Buffer(cuda=True)) and crosses PCIe inside the loop.
         #   replicated: EVERY rank copies the whole buffer over its own link (radiocore.tools.Feeder: two device
@@ -1213,7 +1232,7 @@ def measure_partitioning(run, x, centres, f_in, parallelism, primary, ref=None):
             feeder.close()
         del host
 
-    if primary and rank == 0 and world == 1 and args.cpu_channels > 0 and not rotating and not multi:
+    if args.full and primary and rank == 0 and world == 1 and args.cpu_channels > 0 and not rotating and not multi:
         progress("cpu baseline")
         x_host = x.cpu().numpy()
         ref_audio, result["cpu_baseline"] = cpu_baseline(x_host, f_in, centres, N, C, B, A, kind,
@@ -1405,7 +1424,7 @@ def main():
 
     del refs
     ms_per_step = result["ms_per_step"]
-    if rank == 0 and world == 1 and args.config == "cfg4" and not args.no_extras and not multi:
+    if args.full and rank == 0 and world == 1 and args.config == "cfg4" and not args.no_extras and not multi:
         # the other GPU configurations of BASELINE.json on the same box, outside the headline's timed region
         run.progress("other configurations")
         if "pipelined" not in result:      # (--placement-sets 1: no pair of sets to run lanes on)
