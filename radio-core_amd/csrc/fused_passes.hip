@@ -569,20 +569,6 @@ void fused_real_fft(const FftEngine& e, const float* x, float2* U, float2* tmp, 
     fftk::launch_fft_pass<kRowsOnly>(e.pass_dev(np - 1, e.tmp_stride(), n), count, ldl, stl, s);
 }
 
-void fused_hilbert_ifft_mix(const FftEngine& e, const float2* U, const float* m, float2* u, float2* tmp,
-                            int count, hipStream_t s) {
-    if (count <= 0) return;
-    const int64_t n = e.desc().n;
-    const int np = e.npass();
-    LoadHilbertMask ld{U, (int)n, e.desc().pass[0].in_l};
-    fftk::StorePlainT<false> st0{tmp, 1.0f};
-    fftk::launch_fft_pass<kStridedOnly>(e.pass_dev(0, n, e.tmp_stride()), count, ld, st0, s);
-    middle_passes(e, 1, np - 2, tmp, count, s);
-    fftk::LoadPlainT<false> ldl{tmp};
-    StoreStereoMix stl{m, u};
-    fftk::launch_fft_pass<kRowsOnly>(e.pass_dev(np - 1, e.tmp_stride(), n), count, ldl, stl, s);
-}
-
 void fused_hilbert_ifft(const FftEngine& e, const float2* U, float2* z, float2* tmp, int count, hipStream_t s) {
     if (count <= 0) return;
     const int64_t n = e.desc().n;

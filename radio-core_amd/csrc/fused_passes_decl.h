@@ -18,12 +18,6 @@ void fused_tuner_ifft(const FftEngine& e, const TunerGather& g, float2* out, flo
 void fused_real_fft(const FftEngine& e, const float* x, float2* U, float2* tmp, int count, int keep,
                     hipStream_t s);
 
-// pll.py:34 + wbfm.py:83,86-87: z = ifft(h U) (scipy.signal.hilbert's one-sided mask as the
-// load of the first pass), then s2 = Im(z^2)/|z^2|, lmr = s2 m 1.0175 and the packed stereo
-// signal u = (m + lmr) + j (m - lmr) as the store of the last pass.  U and u may alias.
-void fused_hilbert_ifft_mix(const FftEngine& e, const float2* U, const float* m, float2* u, float2* tmp,
-                            int count, hipStream_t s);
-
 // scipy.signal.hilbert (pll.py:34): z = ifft(h U) / n for full spectra U [count][n] of real signals; U and z may alias.
 void fused_hilbert_ifft(const FftEngine& e, const float2* U, float2* z, float2* tmp, int count, hipStream_t s);
 

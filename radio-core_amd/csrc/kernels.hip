@@ -902,21 +902,6 @@ void launch_stereo_unpack(const float2* U, int64_t B, float2* V, int64_t A, int 
     RC_LAUNCH_CHECK();
 }
 
-__global__ __launch_bounds__(kThreads) void k_discriminator_phase(const float* __restrict__ theta,
-                                                                  float* __restrict__ d, int64_t n) {
-    const int c = blockIdx.y;
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const float* tc = theta + (int64_t)c * n;
-    d[(int64_t)c * n + i] = (i == 0) ? 0.f : phase_step_wrapped(tc[i], tc[i - 1]);
-}
-
-void launch_discriminator_phase(const float* theta, float* d, int64_t n, int batch, hipStream_t stream) {
-    if (batch <= 0) return;
-    hipLaunchKernelGGL(k_discriminator_phase, grid2(n, kThreads, batch), dim3(kThreads), 0, stream, theta, d, n);
-    RC_LAUNCH_CHECK();
-}
-
 void launch_discriminator(const float2* iq, float* d, int64_t n, int batch, hipStream_t stream) {
     if (batch <= 0) return;
     hipLaunchKernelGGL(k_discriminator, grid2(n, kThreads, batch), dim3(kThreads), 0, stream, iq, d, n);

@@ -6,7 +6,8 @@
 // CUs and every launch lasts one tile's latency with two waves per SIMD; with W = 8 the same channel is 60 tiles of
 // half the threads -- one wave per SIMD, half the LDS traffic per CU -- and the data is L2-resident anyway, so the
 // 64-byte segments cost nothing.  The translation units that hold tile kernels are therefore compiled twice:
-// as they are (namespace rcfm, W = 16) and with -DRCFM_TILE_W=8 (namespace rcfm::narrow); api.hip picks per call.
+// as they are (namespace rcfm, W = 16) and with -DRCFM_TILE_W=8 (namespace rcfm::narrow); TILE_CALL (api_internal.h)
+// picks per call.
 #pragma once
 
 #ifndef RCFM_TILE_W

@@ -1,0 +1,384 @@
+// The tuner handle (rcfm_tuner_*): the wideband forward FFT of a buffer, then each channel's bins gathered, weighted
+// and transformed back at the channel's bandwidth.
+
+#include "api_internal.h"
+
+using namespace rcfm;
+
+// Rows of the spectrum (row = n_1 consecutive bins, n_1 = the forward plan's first pass length) that channels
+// [first, first + count) read, as a circular window lo..hi: everything but the longest run of unused rows.
+// false: no engine, too few rows, or nothing worth skipping -- the range reads (nearly) the whole spectrum.
+bool rcfm_tuner_s::row_window(int first, int count, FftRowWindow* w, const FftEngine* eng) const {
+    if (!eng) eng = forward_engine.get();
+    if (!eng || count == 0) return false;
+    const int64_t f0 = eng->row_length();
+    const int64_t rows = n / f0;
+    if (rows < 64) return false;
+    std::vector<char> used((size_t)rows, 0);
+    for (int c = first; c < first + count; ++c) {
+        const int64_t centre = (n - roll[c]) % n, h = bw[c] / 2 + 2;
+        const int64_t r0 = (centre - h) / f0 - ((centre - h) < 0 ? 1 : 0), r1 = (centre + h) / f0;
+        for (int64_t r = r0; r <= r1; ++r) used[(size_t)(((r % rows) + rows) % rows)] = 1;
+    }
+    // the longest circular run of unused rows is dropped; everything else is kept
+    int64_t best_len = 0, best_start = 0, run = 0;
+    for (int64_t i = 0; i < 2 * rows; ++i) {
+        if (!used[(size_t)(i % rows)]) {
+            ++run;
+            if (run > best_len && run <= rows) {
+                best_len = run;
+                best_start = i - run + 1;
+            }
+        } else {
+            run = 0;
+        }
+    }
+    if (best_len < rows / 64 || best_len >= rows) return false;   // nothing worth skipping (or nothing used)
+    w->lo = (int)((best_start + best_len) % rows);
+    w->hi = (int)(((best_start - 1) % rows + rows) % rows);
+    return true;
+}
+
+void rcfm_tuner_s::shard(int first, int count) {
+    require_channels(first, count, nch);
+    shard_first = first;
+    shard_count = count;
+    windowed = row_window(first, count, &window);
+    windowed_aligned = forward_aligned && row_window(first, count, &window_aligned, forward_aligned.get());
+}
+
+// The same window in bins: [first_bin, first_bin + nbins) modulo n (nbins = n: everything).
+void rcfm_tuner_s::bin_window(int first, int count, int64_t* first_bin, int64_t* nbins) const {
+    FftRowWindow w{0, 0};
+    if (count == 0) {            // a rank that owns no channels (C < G) reads nothing
+        *first_bin = 0;
+        *nbins = 0;
+        return;
+    }
+    if (!row_window(first, count, &w)) {
+        *first_bin = 0;
+        *nbins = n;
+        return;
+    }
+    const int64_t f0 = forward_engine->row_length(), rows = n / f0;
+    *first_bin = (int64_t)w.lo * f0;
+    *nbins = (((int64_t)w.hi - w.lo + rows) % rows + 1) * f0;
+}
+
+// The caller has written the bins channels [first, first + count) read (bin_window) into the spectrum storage,
+// e.g. received them from the GPU that ran the wideband FFT of this buffer: repeat the ends in the halos
+// (what the last FFT pass does for a local load) and accept exactly that channel range.
+void rcfm_tuner_s::adopt(int first, int count, hipStream_t s) {
+    require_channels(first, count, nch);
+    int64_t fb = 0, nb = 0;
+    bin_window(first, count, &fb, &nb);
+    RC_REQUIRE(!ext_window || (first == ext_first && count == ext_count), RCFM_ERR_STATE,
+               "the attached storage holds the window of another channel range (rcfm_tuner_attach_window)");
+    if (halo > 0 && !ext_window) {
+        float2* Xs = spectrum();
+        // segments of the window: [fb, min(fb + nb, n)) and, when it wraps, [0, fb + nb - n)
+        const int64_t seg[2][2] = {{fb, std::min(fb + nb, n)}, {0, fb + nb > n ? fb + nb - n : 0}};
+        for (auto& g : seg) {
+            const int64_t a0 = std::max<int64_t>(g[0], 0), a1 = std::min<int64_t>(g[1], halo);   // bins [0, halo) -> behind the end
+            if (a1 > a0)
+                RC_HIP(hipMemcpyAsync(Xs + n + a0, Xs + a0, sizeof(float2) * (size_t)(a1 - a0), hipMemcpyDeviceToDevice, s));
+            const int64_t b0 = std::max<int64_t>(g[0], n - halo), b1 = std::min<int64_t>(g[1], n);     // bins [n - halo, n) -> in front
+            if (b1 > b0)
+                RC_HIP(hipMemcpyAsync(Xs + (b0 - n), Xs + b0, sizeof(float2) * (size_t)(b1 - b0), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    set_loaded(true, nb < n, first, count);
+}
+
+// The bins [fb, fb + nb) of channels [first, first + count), which must be able to live in a storage of their own,
+// [halo | nb | halo]: a window that neither wraps around bin 0 nor touches the far ends (whose halos repeat the other
+// end of the spectrum).
+void rcfm_tuner_s::window_storage(int first, int count, int64_t* fb, int64_t* nb) const {
+    require_channels(first, count, nch);
+    bool ok = halo > 0 && count > 0;
+    if (ok) {
+        bin_window(first, count, fb, nb);
+        ok = *nb < n && *fb >= halo && *fb + *nb <= n - halo;
+    }
+    RC_REQUIRE(ok, RCFM_ERR_SIZE,
+               "these channels' bins wrap around the ends of the spectrum (or are all of it): no window storage");
+}
+
+rcfm_tuner_s::Band& rcfm_tuner_s::band(int32_t b) {
+    auto it = bands.find(b);
+    if (it == bands.end()) {
+        auto nb = std::make_unique<Band>();
+        nb->geom.build(n, b, 0.5 /* hann */, true);
+        FftPlanDesc probe;
+        if (use_engine() && fft_plan_describe(b, &probe)) nb->engine = std::make_unique<FftEngine>(b);
+        it = bands.emplace(b, std::move(nb)).first;
+    }
+    return *it->second;
+}
+
+// The fast gather's preconditions (fused_passes.hip, LoadTunerGatherFast) for the band of channel `first`: haloed
+// spectrum with 32-bit bases, window argument small enough for the series, no up-sampling Nyquist rule.
+bool rcfm_tuner_s::fast_gather_ok(int first) {
+    if (first < 0 || first >= nch || halo <= 0) return false;
+    const int32_t B = bw[first];
+    const ResampleGeom& g = band(B).geom;
+    const bool series = 6.28318530717958647692 * ((double)(B / 2 + 2) / (double)n) < 0.25;
+    return series && halo >= B / 2 + 1 && g.nyq_mode != NYQ_UP && B <= n;
+}
+
+// Can run() leave angle(x) / pi instead of x for this channel's band?  (engine path only)
+bool rcfm_tuner_s::phase_capable(int first) { return first >= 0 && first < nch && band(bw[first]).engine != nullptr; }
+
+// First pass length n_1 of the band's inverse FFT (0 without an engine): its last pass stores rows of n_1 samples.
+int rcfm_tuner_s::band_row_length(int first) { return phase_capable(first) ? (int)band(bw[first]).engine->row_length() : 0; }
+
+// Padded phase rows (fused_tuner_ifft's theta_pitch) need the last pass to write rows of n_1 samples with no
+// outer line index, i.e. a TWO-pass plan (B <= 262144); three-pass bands keep contiguous phases.
+bool rcfm_tuner_s::band_two_pass(int first) { return phase_capable(first) && band(bw[first]).engine->npass() == 2; }
+
+// Channels [first, first + count) may be read from the loaded spectrum: it was loaded, for a shard and into a storage
+// that hold them, and they share one bandwidth (else bw_code / bw_msg).  `caller` names the entry point in the error.
+void rcfm_tuner_s::require_readable(int first, int count, const char* caller, int bw_code, const char* bw_msg) const {
+    RC_REQUIRE(loaded, RCFM_ERR_STATE, std::string(caller) + " called before rcfm_tuner_load");
+    RC_REQUIRE(!loaded_windowed || (first >= loaded_first && first + count <= loaded_first + loaded_count),
+               RCFM_ERR_STATE,
+               "channel outside the shard the spectrum was loaded for (rcfm_tuner_shard, then rcfm_tuner_load)");
+    RC_REQUIRE(!ext_window || (first >= ext_first && first + count <= ext_first + ext_count), RCFM_ERR_STATE,
+               "channel outside the window the attached storage holds (rcfm_tuner_attach_window)");
+    for (int i = 0; i < count; ++i) RC_REQUIRE(bw[first + i] == bw[first], bw_code, bw_msg);
+}
+
+// theta != nullptr (phase_capable bands only): angle(x) / pi goes to theta [count][B] float32, out is unused.
+void rcfm_tuner_s::run(int first, int count, float2* out, hipStream_t s, float* theta, int theta_pitch,
+                       int narrow_mode) {
+    if (narrow_mode < 0) narrow_mode = opt_narrow;
+    require_channels(first, count, nch);
+    require_readable(first, count, "rcfm_tuner_run", RCFM_ERR_ARG, "channels of one rcfm_tuner_run range must share a bandwidth");
+    if (count == 0) return;
+    const int32_t B = bw[first];
+    Band& bd = band(B);
+    const ResampleGeom& g = bd.geom;
+    if (bd.engine) {
+        // gather + window ride on the first pass of the inverse FFT (fused_passes.h)
+        band_tmp.reserve((size_t)count * bd.engine->tmp_stride() * sizeof(float2));
+        TunerGather tg{spectrum(), n, roll_dev.as<int64_t>() + first, 0.5, g.nyq, g.nneg, g.nyq_mode,
+                       halo ? base_dev.as<int32_t>() + first : nullptr, halo};
+        StageTimer tm(ST_TUNER_IFFT, s);
+        TILE_CALL(narrow_launch(*bd.engine, count, narrow_mode), fused_tuner_ifft, *bd.engine, tg, out, band_tmp.as<float2>(), count, s,
+                  theta, theta_pitch);
+        return;
+    }
+    RC_REQUIRE(theta == nullptr, RCFM_ERR_STATE, "phase output needs the FFT engine");
+    size_t need = 0;
+    FftPlan& inv = bd.inverse.get(FftKind::C2C_INVERSE, (size_t)B, count, true, need);
+    work.reserve(need);
+    {
+        StageTimer tm(ST_TUNER_GATHER, s);
+        launch_spectrum_c2c(spectrum(), 0, n, roll_dev.as<int64_t>() + first, out, B, count,
+                            g.wpos.as<float>(), g.wneg.as<float>(), g.w_merge, g.nyq, g.nneg, g.nyq_mode,
+                            g.scale, s);
+    }
+    {
+        StageTimer tm(ST_TUNER_IFFT, s);
+        inv.exec(out, out, work.get(), s);
+    }
+}
+
+extern "C" {
+
+// ---- tuner -----------------------------------------------------------------
+
+int rcfm_tuner_create(int64_t n, int nch, const int64_t* roll_host, const int32_t* bw_host, rcfm_tuner_t* out) {
+    return guarded([&] {
+        RC_REQUIRE(out != nullptr, RCFM_ERR_ARG, "out is NULL");
+        RC_REQUIRE(n >= 1 && nch >= 0, RCFM_ERR_ARG, "bad tuner size");
+        RC_REQUIRE(nch == 0 || (roll_host && bw_host), RCFM_ERR_ARG, "roll/bw is NULL");
+        auto t = std::make_unique<rcfm_tuner_s>();
+        ArenaScope scope(t->arena);
+        t->n = n;
+        t->nch = nch;
+        t->roll.resize(nch);
+        t->bw.assign(bw_host, bw_host + nch);
+        for (int i = 0; i < nch; ++i) {
+            RC_REQUIRE(bw_host[i] >= 1, RCFM_ERR_ARG, "channel bandwidth must be >= 1");
+            // scipy.signal.resample(domain="freq") also up-samples; the Tuner never does
+            RC_REQUIRE(bw_host[i] <= n, RCFM_ERR_ARG, "channel bandwidth exceeds the input bandwidth");
+            int64_t r = roll_host[i] % n;
+            if (r < 0) r += n;
+            t->roll[i] = r;
+        }
+        if (nch) t->roll_dev.upload(t->roll.data(), sizeof(int64_t) * nch);
+        // halo: whole 128-byte lines on both sides, wide enough for the widest channel
+        int64_t h = 0;
+        for (int i = 0; i < nch; ++i) h = std::max<int64_t>(h, bw_host[i] / 2 + 2);
+        h = (h + 15) / 16 * 16;
+        if (nch && h <= n && n + h < ((int64_t)1 << 31)) {
+            t->halo = h;
+            std::vector<int32_t> base(nch);
+            for (int i = 0; i < nch; ++i) base[i] = (int32_t)((n - t->roll[i]) % n);
+            t->base_dev.upload(base.data(), sizeof(int32_t) * nch);
+        }
+        FftPlanDesc probe;
+        if (use_engine() && fft_plan_describe(n, &probe)) {
+            t->forward_engine = std::make_unique<FftEngine>(n);
+            int64_t tmp_elems = t->forward_engine->tmp_stride();
+            int64_t order[3];
+            if (fft_plan_aligned_order(t->forward_engine->desc(), order)) {
+                t->forward_aligned = std::make_unique<FftEngine>(n, order, 3, 2);
+                tmp_elems = std::max(tmp_elems, t->forward_aligned->tmp_stride());
+            }
+            t->forward_tmp.reset(sizeof(float2) * (size_t)tmp_elems);
+        }
+        t->X.reset(t->own_spectrum_bytes());
+        if (!t->forward_engine) {
+            t->forward = std::make_unique<FftPlan>(FftKind::C2C_FORWARD, (size_t)n, 1, false);
+            t->forward_work.reserve(t->forward->work_bytes());
+        }
+        *out = t.release();
+    });
+}
+
+int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(t && x, RCFM_ERR_ARG, "NULL argument");
+        ArenaScope scope(t->arena);
+        RC_REQUIRE(!t->ext_window, RCFM_ERR_STATE,
+                   "rcfm_tuner_load needs storage for the whole spectrum: a window is attached (rcfm_tuner_attach_window)");
+        {
+            StageTimer tm(ST_TUNER_FFT, as_stream(stream));
+            bool halo_done = false;
+            if (t->forward_engine) {
+                // the last pass writes the halos itself (bins near both ends are stored twice): no copy launches
+                const bool al = t->use_aligned();
+                const FftEngine& eng = al ? *t->forward_aligned : *t->forward_engine;
+                FftRowWindow w = al ? (t->windowed_aligned ? t->window_aligned : FftRowWindow{0, (int)(t->n / eng.row_length()) - 1, 0})
+                                    : (t->windowed ? t->window : FftRowWindow{0, (int)(t->n / eng.row_length()) - 1, 0});
+                w.halo = (int)t->halo;
+                halo_done = t->halo > 0;
+                // (aligned plan: x -> the spectrum storage as scratch -> forward_tmp -> the spectrum, no pass in place)
+                eng.c2c(static_cast<const float2*>(x), t->spectrum(), t->forward_tmp.as<float2>(), 1, false, 1.0f,
+                        as_stream(stream), &w, al ? t->X.as<float2>() : nullptr);
+            } else {
+                t->forward_work.reserve(t->forward->work_bytes());
+                t->forward->exec(const_cast<void*>(x), t->spectrum(), t->forward_work.get(), as_stream(stream));
+            }
+            if (t->halo && !halo_done) {
+                float2* X = t->spectrum();
+                const size_t hb = sizeof(float2) * (size_t)t->halo;
+                RC_HIP(hipMemcpyAsync(X - t->halo, X + t->n - t->halo, hb, hipMemcpyDeviceToDevice, as_stream(stream)));
+                RC_HIP(hipMemcpyAsync(X + t->n, X, hb, hipMemcpyDeviceToDevice, as_stream(stream)));
+            }
+        }
+        t->set_loaded(true, t->forward_engine && (t->use_aligned() ? t->windowed_aligned : t->windowed), t->shard_first,
+                      t->shard_count);
+    });
+}
+
+int rcfm_tuner_shard(rcfm_tuner_t t, int first, int count) {
+    return guarded([&] {
+        RC_REQUIRE(t != nullptr, RCFM_ERR_ARG, "NULL argument");
+        t->shard(first, count);
+    });
+}
+
+int rcfm_tuner_run(rcfm_tuner_t t, int first, int count, void* out, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(t && out, RCFM_ERR_ARG, "NULL argument");
+        ArenaScope scope(t->arena);
+        t->run(first, count, static_cast<float2*>(out), as_stream(stream));
+    });
+}
+
+int rcfm_tuner_spectrum(rcfm_tuner_t t, void** X) {
+    return guarded([&] {
+        RC_REQUIRE(t && X, RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(!t->ext_window, RCFM_ERR_STATE, "a window is attached: the whole spectrum is not on this device");
+        *X = t->spectrum();
+    });
+}
+
+int rcfm_tuner_spectrum_layout(rcfm_tuner_t t, int64_t* halo, int64_t* n) {
+    return guarded([&] {
+        RC_REQUIRE(t && halo && n, RCFM_ERR_ARG, "NULL argument");
+        *halo = t->halo;
+        *n = t->n;
+    });
+}
+
+int rcfm_tuner_attach_spectrum(rcfm_tuner_t t, void* storage, int loaded_first, int loaded_count) {
+    return guarded([&] {
+        RC_REQUIRE(t != nullptr, RCFM_ERR_ARG, "NULL argument");
+        if (loaded_count > 0) require_channels(loaded_first, loaded_count, t->nch);
+        ArenaScope scope(t->arena);
+        t->ext = static_cast<float2*>(storage);
+        t->ext_window = false;
+        // the handle's own [halo | n | halo] buffer is not needed while the caller supplies the storage
+        const size_t own_bytes = t->own_spectrum_bytes();
+        if (storage != nullptr) t->X.reset(0);
+        else if (t->X.bytes() < own_bytes) t->X.reset(own_bytes);
+        // what the storage holds: the bins of channels [loaded_first, loaded_first + loaded_count), or nothing yet
+        int64_t fb = 0, nb = t->n;
+        if (loaded_count > 0) t->bin_window(loaded_first, loaded_count, &fb, &nb);
+        t->set_loaded(loaded_count > 0, nb < t->n, loaded_first, std::max(loaded_count, 0));
+    });
+}
+
+int rcfm_tuner_window_layout(rcfm_tuner_t t, int first, int count, int64_t* halo, int64_t* nbins) {
+    return guarded([&] {
+        RC_REQUIRE(t && halo && nbins, RCFM_ERR_ARG, "NULL argument");
+        int64_t fb = 0, nb = 0;
+        t->window_storage(first, count, &fb, &nb);
+        *halo = t->halo;
+        *nbins = nb;
+    });
+}
+
+int rcfm_tuner_attach_window(rcfm_tuner_t t, void* storage, int first, int count) {
+    return guarded([&] {
+        RC_REQUIRE(t && storage, RCFM_ERR_ARG, "NULL argument");
+        int64_t fb = 0, nb = 0;
+        t->window_storage(first, count, &fb, &nb);
+        t->X.reset(0);
+        // bin b of the window sits at storage[halo + b - fb]: `ext` is where bin -halo would be
+        t->ext = static_cast<float2*>(storage) - fb;
+        t->ext_window = true;
+        t->ext_first = first;
+        t->ext_count = count;
+        t->set_loaded(false, false, first, 0);
+    });
+}
+
+int rcfm_tuner_set_option(rcfm_tuner_t t, int option, int value) {
+    return guarded([&] {
+        RC_REQUIRE(t, RCFM_ERR_ARG, "NULL handle");
+        switch (option) {
+            case RCFM_TUNER_OPT_NARROW_TILES:
+                RC_REQUIRE(value >= 0 && value <= 2, RCFM_ERR_ARG, "narrow tiles: 0 never, 1 automatic, 2 always");
+                t->opt_narrow = value;
+                break;
+            case RCFM_TUNER_OPT_ALIGNED_PLAN: t->opt_aligned = value != 0; break;
+            default: RC_REQUIRE(false, RCFM_ERR_ARG, "unknown tuner option");
+        }
+    });
+}
+
+int rcfm_tuner_window(rcfm_tuner_t t, int first, int count, int64_t* first_bin, int64_t* nbins) {
+    return guarded([&] {
+        RC_REQUIRE(t && first_bin && nbins, RCFM_ERR_ARG, "NULL argument");
+        require_channels(first, count, t->nch);
+        t->bin_window(first, count, first_bin, nbins);
+    });
+}
+
+int rcfm_tuner_adopt(rcfm_tuner_t t, int first, int count, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(t != nullptr, RCFM_ERR_ARG, "NULL argument");
+        t->adopt(first, count, as_stream(stream));
+    });
+}
+
+int rcfm_tuner_destroy(rcfm_tuner_t t) {
+    return guarded([&] { delete t; });
+}
+
+}  // extern "C"

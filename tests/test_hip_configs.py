@@ -69,24 +69,37 @@ def test_run_all_every_demodulator(rc, oracle, kind, chunk):
             assert rel_err(audio[c.index], want) <= TOL, (kind, buf, c.index)
 
 
-@pytest.mark.parametrize("A", [12150, 12006])
-@pytest.mark.parametrize("kind", ["FM", "MFM"])
+@pytest.mark.parametrize("kind,A", [("FM", 12150), ("FM", 12006), ("MFM", 12150), ("MFM", 12006), ("WBFM", 12006)])
 def test_run_all_a_not_multiple_of_four(rc, oracle, kind, A):
-    """A % 4 != 0 takes MFM off the packed-pair decimation (api.hip run_chunk) onto the generic de-emphasis
-    kernels.  A = 12150 = 2 * 3^5 * 5^2 stays on the FFT engine but is no tile-aligned decimation of B = 60000
-    (pair FFT -> full spectrum -> unpack -> real-output inverse FFT); A = 12006 has the prime factors 23 and 29:
-    every transform of the demodulator goes through rocFFT."""
+    """A % 4 != 0 takes MFM off the packed-pair decimation (demod.hip, rcfm_demod_s::run_chunk) onto the generic
+    de-emphasis kernels.  A = 12150 = 2 * 3^5 * 5^2 stays on the FFT engine but is no tile-aligned decimation of
+    B = 60000 (pair FFT -> full spectrum -> unpack -> real-output inverse FFT); A = 12006 has the prime factors 23 and
+    29: every transform of the demodulator goes through rocFFT.  For WBFM that is the only route with separate
+    `hilbert_mask` and `stereo_mix` stages (rcfm_demod_s::run_wbfm_rocfft), and it leaves no DC bin, so the de-emphasis
+    runs unfused (generic FIR, then `dc_clip`) although A * 2 % 4 == 0: the stage profile must show that route ran."""
+    from radiocore._internal import hip
+    lib = hip.lib()
     N, B, C = 1_200_000, 60000, 3
+    stereo = kind == "WBFM"
+    ch = 2 if stereo else 1
     centres = workloads.channel_grid(C, 70000)
     tuner, ref = _pair(rc, oracle, kind, centres, B, A, N)
-    for buf in range(2):
-        x = np.roll(workloads.wideband(N, ref.input_frequency, centres, B, gain=0.35, stereo=False), 99 * buf)
-        tuner.load(x)
-        ref.load(x)
-        audio = tuner.run_all()
-        for c in ref.channels():
-            want = np.asarray(c.demodulator.run(ref.run_pruned(c.index))).reshape(A, 1)
-            assert rel_err(audio[c.index], want) <= TOL, (kind, buf, c.index)
+    hip.check(lib.rcfm_profile_enable((1 << lib.rcfm_profile_stage_count()) - 1))
+    hip.check(lib.rcfm_profile_reset())
+    try:
+        for buf in range(2):
+            x = np.roll(workloads.wideband(N, ref.input_frequency, centres, B, gain=0.35, stereo=stereo), 99 * buf)
+            tuner.load(x)
+            ref.load(x)
+            audio = tuner.run_all()
+            for c in ref.channels():
+                want = np.asarray(c.demodulator.run(ref.run_pruned(c.index))).reshape(A, ch)
+                assert rel_err(audio[c.index], want) <= TOL, (kind, buf, c.index)
+        ran = _stages_run(lib, hip)
+    finally:
+        hip.check(lib.rcfm_profile_enable(0))
+    if stereo:
+        assert ran["hilbert_mask"] > 0 and ran["stereo_mix"] > 0 and ran["dc_clip"] > 0, ran
 
 
 @pytest.mark.parametrize("kind,B,A,chunk", [

@@ -54,7 +54,7 @@ class FakeTuner:
         for c in range(first, first + count):
             for b in range(CENTRES[c] - 40, CENTRES[c] + 41):
                 used[(b % n) // ROW] = True
-        # everything but the longest circular run of unused rows (api.hip: rcfm_tuner_s::row_window)
+        # everything but the longest circular run of unused rows (tuner.hip: rcfm_tuner_s::row_window)
         best, start, run = 0, 0, 0
         for i in range(2 * rows):
             if not used[i % rows]:
