@@ -40,7 +40,8 @@
 extern "C" {
 #endif
 
-#define RCFM_VERSION 102 /* 0.1.2: tooling entry points moved to rcfm_tools.h (same symbols), RCFM_OPT_GRAPH */
+#define RCFM_VERSION 102 /* 0.1.2: tooling entry points moved to rcfm_tools.h (same symbols), RCFM_OPT_GRAPH;
+                            demodulator kind RCFM_AM (no new entry points) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -54,7 +55,11 @@ typedef enum rcfm_status {
 typedef enum rcfm_demod_kind {
     RCFM_FM = 0,  /* radiocore/analog/fm.py:26-72   */
     RCFM_MFM = 1, /* radiocore/analog/mfm.py:29-71  */
-    RCFM_WBFM = 2 /* radiocore/analog/wbfm.py:32-105 */
+    RCFM_WBFM = 2, /* radiocore/analog/wbfm.py:32-105 */
+    /* AM envelope detector (no reference counterpart), one audio channel, no state; tau is ignored.  Per channel and
+       buffer, float32: e = |x| (B samples); v = Decimate(B -> A)(e), the same periodic-Hamming resample as FM;
+       c = mean(v), the carrier level; audio = clip(v / c - 1, -0.999, 0.999), or zeros when !(c > 0). */
+    RCFM_AM = 3
 } rcfm_demod_kind;
 
 typedef struct rcfm_tuner_s* rcfm_tuner_t;

@@ -78,6 +78,8 @@ enum Stage : int {
     ST_DEEMPH_STATE,    // W5b
     ST_DC_CLIP,         // W5c
     ST_LDS_CHAIN,       // T2 + F1 + F2 of narrow FM / MFM channels in one kernel (lds_chain.h)
+    ST_ENVELOPE,        // A1  |x| of AM channels (when the tuner did not store it)
+    ST_AM_TAIL,         // A2  AM carrier normalisation and clip
     ST_COUNT
 };
 
@@ -259,5 +261,5 @@ struct rcfm_tuner_s {
     bool band_two_pass(int first);
     void require_readable(int first, int count, const char* caller, int bw_code, const char* bw_msg) const;
     void run(int first, int count, float2* out, hipStream_t s, float* theta = nullptr, int theta_pitch = 0,
-             int narrow_mode = -1);
+             int narrow_mode = -1, bool envelope = false);
 };

@@ -1,5 +1,5 @@
-// The demodulator handle (rcfm_demod_*): the per-chunk kernel chains of FM / MFM / WBFM.run, one method per route a
-// chunk can take, and rcfm_pipeline_run, which joins a tuner to a demodulator.
+// The demodulator handle (rcfm_demod_*): the per-chunk kernel chains of FM / MFM / WBFM / AM.run, one method per route
+// a chunk can take, and rcfm_pipeline_run, which joins a tuner to a demodulator.
 
 #include <cmath>
 #include <cstring>
@@ -8,7 +8,7 @@
 
 using namespace rcfm;
 
-// The per-chunk kernel chains of FM / MFM / WBFM.run.
+// The per-chunk kernel chains of FM / MFM / WBFM / AM.run.
 struct rcfm_demod_s {
     Arena* arena = arena_enter_handle();   // rcfm_arena_bind at creation
     ~rcfm_demod_s() {
@@ -108,6 +108,9 @@ struct rcfm_demod_s {
         return A % (2 * n1) == 0 && A / n1 >= 16 && fft_plan_describe(A, &pa, 0, fa, 2);
     }
 
+    // MFM and WBFM carry de-emphasis state from buffer to buffer; FM and AM carry none.
+    bool stateful() const { return kind == RCFM_MFM || kind == RCFM_WBFM; }
+
     void alloc() {
         const size_t c = (size_t)chunk;
         tiles = fir_tiles(A);
@@ -117,12 +120,12 @@ struct rcfm_demod_s {
             buf_Z.reset(c * B * sizeof(float2));      // analytic pilot, then the packed L/R signal
             buf_V.reset(c * A * sizeof(float2));      // packed audio spectrum -> l + j r
         } else {
-            buf_m.reset(c * B * sizeof(float));                    // discriminator output
+            buf_m.reset(c * B * sizeof(float));                    // discriminator output (AM: the envelope)
             buf_P.reset(c * (B / 2 + 1) * sizeof(float2));          // its half spectrum
             buf_V.reset(c * (A / 2 + 1) * sizeof(float2));          // resampled half spectrum
             if (kind == RCFM_MFM) buf_v.reset(c * A * sizeof(float));
         }
-        if (kind != RCFM_FM) partial.reset((size_t)chunk * ch * tiles * sizeof(float));
+        if (stateful()) partial.reset((size_t)chunk * ch * tiles * sizeof(float));
         buf_dc.reset((size_t)chunk * sizeof(float2));
         FftPlanDesc probe;
         if (use_engine() && fft_plan_describe(B, &probe) && fft_plan_describe(A, &probe)) {
@@ -182,7 +185,7 @@ struct rcfm_demod_s {
     }
 
     void reset_state(hipStream_t s) {
-        if (kind == RCFM_FM) return;
+        if (!stateful()) return;
         std::vector<float> all((size_t)C * ch * 50);
         for (size_t i = 0; i < all.size(); ++i) all[i] = zi_h[i % 50];
         RC_HIP(hipMemcpyAsync(state_ptr(), all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice, s));
@@ -271,7 +274,8 @@ struct rcfm_demod_s {
     }
 
     // Does run_chunk take the samples' phases (theta = angle(x) / pi, float32 [cnt][B]) instead of iq?
-    bool phase_capable() const { return eng_B != nullptr && (kind != RCFM_WBFM || B % 4 == 0); }
+    // AM never: its chain starts from |x|, which the phases do not hold (the tuner stores the envelope for it instead).
+    bool phase_capable() const { return eng_B != nullptr && kind != RCFM_AM && (kind != RCFM_WBFM || B % 4 == 0); }
 
     // One chunk of channels [first, first + cnt) from iq (or the tuner's phases) to audio, by one of the routes below.
     void run_chunk(int first, int cnt, const float2* iq, float* audio, hipStream_t s, const float* theta = nullptr,
@@ -283,20 +287,47 @@ struct rcfm_demod_s {
                 run_wbfm_rocfft(first, cnt, iq, audio, s, theta);
             return;
         }
+        if (kind == RCFM_AM) {
+            run_am(cnt, iq, audio, s, false);
+            return;
+        }
         // fm.py:60-66  discriminator, then Decimate(B -> A) into the audio (FM) or into v, which mfm.py:63-65 de-emphasises
         if (theta == nullptr) {
             StageTimer tm(ST_DISC, s);
             launch_discriminator(iq, buf_m.as<float>(), B, cnt, s);
         }
         float* dst = (kind == RCFM_FM) ? audio : buf_v.as<float>();
-        if (eng_B && eng_Ad && opt_decim_tile && ((int64_t)A % 4 == 0 || kind == RCFM_FM) &&
+        run_real(cnt, dst, s, theta, rows);
+        if (kind == RCFM_MFM) run_deemph(dst, audio, first, cnt, s, /*generic_fir=*/!eng_B);   // rocFFT left no DC bin
+    }
+
+    // Decimate(B -> A) of the real signals in buf_m (or of the phase steps of theta) into dst, by the first route that
+    // applies: the decimating tile, the engine with a separate resample, rocFFT.  The engine routes leave the DC bin of
+    // every channel's resampled spectrum in buf_dc; rocFFT leaves none (returns false).
+    bool run_real(int cnt, float* dst, hipStream_t s, const float* theta, PhaseRows rows) {
+        if (eng_B && eng_Ad && opt_decim_tile && ((int64_t)A % 4 == 0 || kind != RCFM_MFM) &&
             TILE_CALL(narrow(cnt), fused_fft_decim_ifft_applies, *eng_B, *eng_Ad, (cnt + 1) / 2))
             run_pair_decim(cnt, dst, s, theta, rows);
         else if (eng_B)
             run_fm_engine(cnt, dst, s, theta, rows);
-        else
+        else {
             run_fm_rocfft(cnt, dst, s);
-        if (kind == RCFM_MFM) run_deemph(dst, audio, first, cnt, s, /*generic_fir=*/!eng_B);   // rocFFT left no DC bin
+            return false;
+        }
+        return true;
+    }
+
+    // AM (include/rcfm.h, RCFM_AM): envelope |x| into buf_m -- unless the tuner's last pass already stored it there
+    // (envelope_ready, rcfm_pipeline_run) --, FM's real-signal routes straight into the audio, then the carrier
+    // normalisation in place.  Its mean comes from the DC bin when the route left one.
+    void run_am(int cnt, const float2* iq, float* audio, hipStream_t s, bool envelope_ready) {
+        if (!envelope_ready) {
+            StageTimer tm(ST_ENVELOPE, s);
+            launch_envelope(iq, buf_m.as<float>(), (int64_t)cnt * B, s);
+        }
+        const bool dc = run_real(cnt, audio, s, nullptr, PhaseRows{});
+        StageTimer tm(ST_AM_TAIL, s);
+        launch_am_tail(audio, A, cnt, dc ? buf_dc.as<float2>() : nullptr, s);
     }
 
     // wbfm.py:77-80  FM(B->B) and the pilot band-pass
@@ -531,7 +562,7 @@ struct rcfm_demod_s {
     // call in a row with them.  false: the caller launches the chain itself.
     bool run_graphed(int first, const float2* iq, float* audio, hipStream_t s) {
         if (!opt_graph || !eng_B || g_prof.mask != 0 || state_buf->armed) return false;
-        const float* st = kind == RCFM_FM ? nullptr : state_ptr();
+        const float* st = stateful() ? state_ptr() : nullptr;
         for (auto& g : graphs)
             if (g.iq == iq && g.audio == audio && g.first == first && g.state == st) {
                 g.used = ++graph_tick;
@@ -580,7 +611,7 @@ extern "C" {
 int rcfm_demod_create(int kind, int C, int B, int A, double tau, int chunk, rcfm_demod_t* out) {
     return guarded([&] {
         RC_REQUIRE(out != nullptr, RCFM_ERR_ARG, "out is NULL");
-        RC_REQUIRE(kind >= RCFM_FM && kind <= RCFM_WBFM, RCFM_ERR_ARG, "unknown demodulator kind");
+        RC_REQUIRE(kind >= RCFM_FM && kind <= RCFM_AM, RCFM_ERR_ARG, "unknown demodulator kind");
         RC_REQUIRE(C >= 1 && B >= 2 && A >= 1, RCFM_ERR_ARG, "bad demodulator size");
         auto d = std::make_unique<rcfm_demod_s>();
         ArenaScope scope(d->arena);
@@ -614,7 +645,7 @@ int rcfm_demod_create(int kind, int C, int B, int A, double tau, int chunk, rcfm
             d->pilot_g.upload(g.data(), g.size() * sizeof(float));
             d->side_tap = (B % 2) ? (float)(0.23 * std::cos(kPi / (double)B)) : 0.23f;
         }
-        if (kind != RCFM_FM) {
+        if (d->stateful()) {
             deemphasis_design(A, tau, d->taps_h, d->zi_h);
             d->taps.upload(d->taps_h, sizeof(d->taps_h));
             d->state_buf->reset((size_t)C * d->ch * 50 * sizeof(float));
@@ -651,7 +682,7 @@ int rcfm_demod_reset_state(rcfm_demod_t d, void* stream) {
 int rcfm_demod_get_state(rcfm_demod_t d, float* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
-        if (d->kind == RCFM_FM) return;
+        if (!d->stateful()) return;
         RC_HIP(hipMemcpyAsync(state_host, d->state_ptr(), (size_t)d->C * d->ch * 50 * sizeof(float),
                               hipMemcpyDeviceToHost, as_stream(stream)));
         RC_HIP(hipStreamSynchronize(as_stream(stream)));
@@ -661,7 +692,7 @@ int rcfm_demod_get_state(rcfm_demod_t d, float* state_host, void* stream) {
 int rcfm_demod_set_state(rcfm_demod_t d, const float* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
-        if (d->kind == RCFM_FM) return;
+        if (!d->stateful()) return;
         RC_HIP(hipMemcpyAsync(d->state_ptr(), state_host, (size_t)d->C * d->ch * 50 * sizeof(float),
                               hipMemcpyHostToDevice, as_stream(stream)));
         RC_HIP(hipStreamSynchronize(as_stream(stream)));
@@ -675,7 +706,7 @@ int rcfm_demod_bind_state(rcfm_demod_t single, rcfm_demod_t batched, int index, 
                        single->tau == batched->tau,
                    RCFM_ERR_ARG, "bind_state needs demodulators of one class, audio rate and time constant");
         require_channels(index, single->C, batched->C);
-        if (single->kind == RCFM_FM) return;   // fm.py carries no state
+        if (!single->stateful()) return;   // fm.py carries no state, nor does AM
         const size_t per = (size_t)single->C * single->ch * 50;
         const size_t slot = batched->state_off + (size_t)index * single->ch * 50;
         float* dst = batched->state_at(index);
@@ -768,9 +799,20 @@ int rcfm_pipeline_run(rcfm_tuner_t t, rcfm_demod_t d, int first, int count, void
             const int c0 = first + off, cnt = std::min(d->chunk, count - off);
             float* out_c = static_cast<float*>(audio) + (size_t)off * d->A * d->ch;
             RC_REQUIRE(t->bw[c0] == d->B, RCFM_ERR_SIZE, "input_sig size and input_size mismatch");
-            // RCFM_OPT_LDS_CHAIN = 0: the multi-pass launches.
-            if (d->opt_lds_chain && d->kind != RCFM_WBFM && lds_chain_supported(d->B, d->A) && t->fast_gather_ok(c0)) {
+            // RCFM_OPT_LDS_CHAIN = 0: the multi-pass launches.  The chain computes the FM discriminator: FM / MFM only.
+            if (d->opt_lds_chain && (d->kind == RCFM_FM || d->kind == RCFM_MFM) && lds_chain_supported(d->B, d->A) &&
+                t->fast_gather_ok(c0)) {
                 d->run_lds_chain(*t, c0, cnt, out_c, s);
+                continue;
+            }
+            // AM's counterpart of the phase link: the tuner's last pass stores |x| (float32, contiguous) straight into
+            // the buffer the envelope kernel would fill.  RCFM_OPT_PHASE_LINK = 0: complex hand-over + envelope kernel.
+            if (d->kind == RCFM_AM && d->opt_phase_link && t->phase_capable(c0)) {
+                {
+                    ArenaScope ts(t->arena);
+                    t->run(c0, cnt, nullptr, s, d->buf_m.as<float>(), 0, d->opt_narrow, /*envelope=*/true);
+                }
+                d->run_am(cnt, nullptr, out_c, s, /*envelope_ready=*/true);
                 continue;
             }
             // Every demodulator starts with the FM discriminator, which only needs the samples' phases:

@@ -493,8 +493,19 @@ struct StorePhase {
     }
 };
 
+// Its AM counterpart (RCFM_AM): the envelope |x| as float32, x scaled as StorePlainT<true> stores it (same rounding as
+// the envelope kernel applied to the complex hand-over).
+struct StoreEnvelope {
+    float* e;
+    float scale;
+    __device__ __forceinline__ void operator()(const LineId&, int, int64_t base, unsigned off, float2 v) const {
+        const float re = v.y * scale, im = v.x * scale;
+        (e + base)[off] = sqrtf(re * re + im * im);
+    }
+};
+
 void fused_tuner_ifft(const FftEngine& e, const TunerGather& g, float2* out, float2* tmp, int count,
-                      hipStream_t s, float* theta, int theta_pitch) {
+                      hipStream_t s, float* theta, int theta_pitch, bool envelope) {
     if (count <= 0) return;
     const int64_t B = e.desc().n;
     const int np = e.npass();
@@ -548,7 +559,10 @@ void fused_tuner_ifft(const FftEngine& e, const TunerGather& g, float2* out, flo
             last.out_batch = (B / last.p.out_k) * (int64_t)theta_pitch;
             last.p.out_k = theta_pitch;
         }
-        fftk::launch_fft_pass<kRowsOnly>(last, count, ldl, StorePhase{theta}, s);
+        if (envelope)
+            fftk::launch_fft_pass<kRowsOnly>(last, count, ldl, StoreEnvelope{theta, (float)(1.0 / (double)g.N)}, s);
+        else
+            fftk::launch_fft_pass<kRowsOnly>(last, count, ldl, StorePhase{theta}, s);
         return;
     }
     fftk::StorePlainT<true> stl{out, (float)(1.0 / (double)g.N)};   // ifft (1/B) * (B/N)

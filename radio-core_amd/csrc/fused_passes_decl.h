@@ -9,8 +9,9 @@ RCFM_DECL_NS_OPEN
 // theta_pitch > 0: phase k_1 + n_1 k_2 of a channel goes to theta[k_2 theta_pitch + k_1] (n_1 = e's first pass length; a
 // channel then occupies (B / n_1) theta_pitch values): rows of n_1 = 100 phases start every 400 bytes and their 64-byte
 // store segments straddle lines; at a pitch of 112 they are aligned (PhaseRows describes the layout to the reader).
+// envelope: theta receives |x| instead of angle(x) / pi (AM, RCFM_AM) -- same layout.
 void fused_tuner_ifft(const FftEngine& e, const TunerGather& g, float2* out, float2* tmp, int count,
-                      hipStream_t s, float* theta = nullptr, int theta_pitch = 0);
+                      hipStream_t s, float* theta = nullptr, int theta_pitch = 0, bool envelope = false);
 
 
 // Forward FFT of real signals x [count][n] -> full complex spectrum U [count][n].

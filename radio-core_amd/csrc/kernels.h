@@ -116,4 +116,12 @@ void launch_fir_state(const float* x, int64_t n, int ch, int batch, const float*
 void launch_dc_clip(float* y, int64_t n, int ch, int batch, const float* partial, int nparts,
                     hipStream_t stream);
 
+// AM (RCFM_AM): e = |x| of n complex samples (iq [n] complex64 -> e [n] float32; a batch of channels is one flat run).
+// 16-byte accesses when both pointers are 16-byte aligned.
+void launch_envelope(const float2* iq, float* e, int64_t n, hipStream_t stream);
+// AM's tail, in place on y [batch][n]: y = clip(y / c - 1, +-0.999) with c = the channel's mean, zeros when !(c > 0).
+// dc != nullptr ([batch], from launch_spectrum_real_full / the decimating tile): c = dc[c].x, the DC bin of the
+// resampled spectrum (= the mean of y); else every channel reduces its own y first.
+void launch_am_tail(float* y, int64_t n, int batch, const float2* dc, hipStream_t stream);
+
 }  // namespace rcfm

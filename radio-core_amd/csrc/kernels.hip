@@ -853,6 +853,72 @@ __global__ __launch_bounds__(kThreads) void k_dc_clip(float* __restrict__ y, int
     y[(int64_t)c * total + i] = v;
 }
 
+// AM (RCFM_AM) envelope: e = |x|.  VEC (both pointers 16-byte aligned): thread q owns samples 4q .. 4q + 3 -- two
+// 16-byte loads and one 16-byte store; the ragged last quad (n % 4) takes scalar accesses.  Else one sample per thread.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_envelope(const float2* __restrict__ iq, float* __restrict__ e, int64_t n) {
+    auto mag = [](float re, float im) { return sqrtf(re * re + im * im); };
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (!VEC) {
+        if (t < n) e[t] = mag(iq[t].x, iq[t].y);
+        return;
+    }
+    const int64_t i0 = 4 * t;
+    if (i0 + 4 <= n) {
+        const float4 a = *reinterpret_cast<const float4*>(iq + i0);
+        const float4 b = *reinterpret_cast<const float4*>(iq + i0 + 2);
+        *reinterpret_cast<float4*>(e + i0) = make_float4(mag(a.x, a.y), mag(a.z, a.w), mag(b.x, b.y), mag(b.z, b.w));
+    } else {
+        for (int64_t i = i0; i < n; ++i) e[i] = mag(iq[i].x, iq[i].y);
+    }
+}
+
+// AM's tail on channel blockIdx.y of y [batch][n], in place: y = clip(y / c - 1, +-0.999), zeros when !(c > 0).
+// c = dc[c].x (the DC bin = the mean of y), or -- dc == nullptr, launched with ONE workgroup per channel -- the
+// workgroup's own float64 sum of the channel.  A workgroup covers 4 kThreads samples per sweep: 16-byte accesses
+// when VEC (n % 4 == 0 and y 16-byte aligned), else four coalesced scalar sweeps.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_am_tail(float* __restrict__ y, int64_t n, const float2* __restrict__ dc) {
+    __shared__ double red[kThreads / 64];
+    const int c = blockIdx.y;
+    const int tid = threadIdx.x;
+    float* yc = y + (int64_t)c * n;
+    float carrier;
+    if (dc != nullptr) {
+        carrier = dc[c].x;
+    } else {
+        double acc = 0.0;
+        for (int64_t i = tid; i < n; i += kThreads) acc += (double)yc[i];
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if ((tid & 63) == 0) red[tid >> 6] = acc;
+        __syncthreads();
+        double tot = 0.0;
+        for (int w = 0; w < kThreads / 64; ++w) tot += red[w];
+        carrier = (float)(tot / (double)n);
+    }
+    const bool live = carrier > 0.f;   // false for 0 and NaN: a silent channel gives zeros
+    auto tail = [&](float v) {
+        if (!live) return 0.f;
+        v = v / carrier - 1.f;
+        return (v < -0.999f) ? -0.999f : ((v > 0.999f) ? 0.999f : v);
+    };
+    const int64_t sweep = 4 * (int64_t)kThreads;
+    for (int64_t b0 = (int64_t)blockIdx.x * sweep; b0 < n; b0 += (int64_t)gridDim.x * sweep) {
+        if (VEC) {
+            const int64_t i = b0 + 4 * tid;
+            if (i < n) {
+                float4 v = *reinterpret_cast<const float4*>(yc + i);
+                *reinterpret_cast<float4*>(yc + i) = make_float4(tail(v.x), tail(v.y), tail(v.z), tail(v.w));
+            }
+        } else {
+            for (int j = 0; j < 4; ++j) {
+                const int64_t i = b0 + j * kThreads + tid;
+                if (i < n) yc[i] = tail(yc[i]);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1044,6 +1110,26 @@ void launch_dc_clip(float* y, int64_t n, int ch, int batch, const float* partial
     const int64_t total = n * ch;
     hipLaunchKernelGGL(k_dc_clip, grid2(total, kThreads, batch), dim3(kThreads), 0, stream, y, total, partial,
                        nparts);
+    RC_LAUNCH_CHECK();
+}
+
+void launch_envelope(const float2* iq, float* e, int64_t n, hipStream_t stream) {
+    if (n <= 0) return;
+    if (((uintptr_t)iq | (uintptr_t)e) % 16 == 0)
+        hipLaunchKernelGGL(k_envelope<true>, grid2((n + 3) / 4, kThreads, 1), dim3(kThreads), 0, stream, iq, e, n);
+    else
+        hipLaunchKernelGGL(k_envelope<false>, grid2(n, kThreads, 1), dim3(kThreads), 0, stream, iq, e, n);
+    RC_LAUNCH_CHECK();
+}
+
+void launch_am_tail(float* y, int64_t n, int batch, const float2* dc, hipStream_t stream) {
+    if (batch <= 0 || n <= 0) return;
+    // without a DC bin one workgroup per channel sums it before rewriting it
+    const dim3 grid = dc != nullptr ? grid2(n, 4 * kThreads, batch) : dim3(1, (unsigned)batch, 1);
+    if (n % 4 == 0 && (uintptr_t)y % 16 == 0)
+        hipLaunchKernelGGL(k_am_tail<true>, grid, dim3(kThreads), 0, stream, y, n, dc);
+    else
+        hipLaunchKernelGGL(k_am_tail<false>, grid, dim3(kThreads), 0, stream, y, n, dc);
     RC_LAUNCH_CHECK();
 }
 

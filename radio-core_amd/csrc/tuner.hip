@@ -148,9 +148,10 @@ void rcfm_tuner_s::require_readable(int first, int count, const char* caller, in
     for (int i = 0; i < count; ++i) RC_REQUIRE(bw[first + i] == bw[first], bw_code, bw_msg);
 }
 
-// theta != nullptr (phase_capable bands only): angle(x) / pi goes to theta [count][B] float32, out is unused.
+// theta != nullptr (phase_capable bands only): angle(x) / pi goes to theta [count][B] float32, out is unused;
+// envelope: |x| instead (AM).
 void rcfm_tuner_s::run(int first, int count, float2* out, hipStream_t s, float* theta, int theta_pitch,
-                       int narrow_mode) {
+                       int narrow_mode, bool envelope) {
     if (narrow_mode < 0) narrow_mode = opt_narrow;
     require_channels(first, count, nch);
     require_readable(first, count, "rcfm_tuner_run", RCFM_ERR_ARG, "channels of one rcfm_tuner_run range must share a bandwidth");
@@ -165,7 +166,7 @@ void rcfm_tuner_s::run(int first, int count, float2* out, hipStream_t s, float* 
                        halo ? base_dev.as<int32_t>() + first : nullptr, halo};
         StageTimer tm(ST_TUNER_IFFT, s);
         TILE_CALL(narrow_launch(*bd.engine, count, narrow_mode), fused_tuner_ifft, *bd.engine, tg, out, band_tmp.as<float2>(), count, s,
-                  theta, theta_pitch);
+                  theta, theta_pitch, envelope);
         return;
     }
     RC_REQUIRE(theta == nullptr, RCFM_ERR_STATE, "phase output needs the FFT engine");

@@ -15,7 +15,8 @@ from radiocore._internal import Injector, hip
 
 __all__ = ["Tuner", "Channel"]
 
-_KINDS = {"FM": hip.RCFM_FM, "MFM": hip.RCFM_MFM, "WBFM": hip.RCFM_WBFM}
+_KINDS = {"FM": hip.RCFM_FM, "MFM": hip.RCFM_MFM, "WBFM": hip.RCFM_WBFM, "AM": hip.RCFM_AM}
+_STATELESS = (hip.RCFM_FM, hip.RCFM_AM)    # kinds without de-emphasis state: nothing to bind or fence
 
 
 @dataclass
@@ -354,7 +355,7 @@ class Tuner(Injector):
         blocks = []
         for i, n, kind, B, A, tau in groups:
             if kind is None:
-                raise ValueError("run_each needs an FM, MFM or WBFM demodulator on every channel")
+                raise ValueError("run_each needs an FM, MFM, WBFM or AM demodulator on every channel")
             ch = 2 if kind == hip.RCFM_WBFM else 1
             audio = hip.empty((n, A, ch), self._torch.float32)
             hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, 0), i, n,
@@ -407,7 +408,7 @@ class Tuner(Injector):
             if opts[3] != 1:   # (rcfm_pipeline_run hands the same setting to the tuner's inverse FFT of each chunk)
                 hip.check(self._lib.rcfm_demod_set_option(h, hip.RCFM_OPT_NARROW_TILES, opts[3]))
             self._bind_states(key, self._batched[key])
-            if self._state_fence and kind != hip.RCFM_FM:    # after the binding: the fence travels with the state buffer
+            if self._state_fence and kind not in _STATELESS:    # after the binding: the fence travels with the state buffer
                 hip.check(self._lib.rcfm_demod_set_option(h, hip.RCFM_OPT_STATE_FENCE, 1))
         elif self._bound_version.get(key) != self._version:
             self._bind_states(key, self._batched[key])
@@ -420,10 +421,10 @@ class Tuner(Injector):
         what it has carried so far), and further batched handles of the same geometry (another `chunk`) share the
         first one's buffer.  Mixing ``ch.demodulator.run(tuner.run(i))`` and ``run_all()`` across buffers then gives
         what the reference's loop gives.  O(C) Python, once per change of the channel list; a demodulator whose own
-        librcfm handle does not exist yet (it is created on first use) binds when it does; FM carries no state."""
+        librcfm handle does not exist yet (it is created on first use) binds when it does; FM and AM carry no state."""
         kind, C, B, A, tau = key[:5]
         self._bound_version[key] = self._version
-        if kind == hip.RCFM_FM:
+        if kind in _STATELESS:
             return
         owner_key = (kind, C, B, A, tau)
         owner = self._state_owner.get(owner_key)
@@ -449,7 +450,7 @@ class Tuner(Injector):
         that touches the shared de-emphasis state waits for the previous one (rcfm_demod_set_option, RCFM_OPT_STATE_FENCE)."""
         self._state_fence = True
         for key, h in self._batched.items():
-            if key[0] != hip.RCFM_FM:
+            if key[0] not in _STATELESS:
                 hip.check(self._lib.rcfm_demod_set_option(h.value, hip.RCFM_OPT_STATE_FENCE, 1))
 
     def _lane_clone(self):
