@@ -41,7 +41,7 @@ extern "C" {
 #endif
 
 #define RCFM_VERSION 102 /* 0.1.2: tooling entry points moved to rcfm_tools.h (same symbols), RCFM_OPT_GRAPH;
-                            demodulator kind RCFM_AM (no new entry points) */
+                            demodulator kinds RCFM_AM, RCFM_USB, RCFM_LSB (no new entry points) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -59,8 +59,20 @@ typedef enum rcfm_demod_kind {
     /* AM envelope detector (no reference counterpart), one audio channel, no state; tau is ignored.  Per channel and
        buffer, float32: e = |x| (B samples); v = Decimate(B -> A)(e), the same periodic-Hamming resample as FM;
        c = mean(v), the carrier level; audio = clip(v / c - 1, -0.999, 0.999), or zeros when !(c > 0). */
-    RCFM_AM = 3
+    RCFM_AM = 3,
+    /* Single sideband (no reference counterpart), one audio channel, no state; tau is ignored.  The channel centre is the
+       suppressed carrier.  Per channel and buffer, for the B channel samples x:
+         X = fft(x);  H_usb[k] = 2 for 1 <= k <= (B-1)/2, else 0 (DC and, for even B, the bin B/2 are dropped);
+         H_lsb[k] = H_usb[(B - k) mod B];  s = Re(ifft(H X));  v = Decimate(B -> A)(s), the resample FM and AM use;
+         g = sqrt(mean(v^2));  audio = clip(RCFM_SSB_LEVEL v / g, -0.999, 0.999), or zeros when !(g > 0).
+       The per-buffer RMS normalisation makes the audio level independent of the station's level.
+       Value 4 is unassigned: rcfm_demod_create refuses it (and everything above 6) as an unknown kind. */
+    RCFM_USB = 5,
+    RCFM_LSB = 6
 } rcfm_demod_kind;
+
+/* Audio RMS of a USB / LSB channel: a single tone peaks at 0.354, Gaussian noise reaches the clip at 4 sigma. */
+#define RCFM_SSB_LEVEL 0.25f
 
 typedef struct rcfm_tuner_s* rcfm_tuner_t;
 typedef struct rcfm_demod_s* rcfm_demod_t;

@@ -69,9 +69,12 @@ int rcfm_tuner_set_option(rcfm_tuner_t t, int option, int value);
  *   RCFM_OPT_LDS_DEEMPH   narrow MFM channels: de-emphasis, mean removal and clip inside the LDS chain (0: the
  *                         de-emphasis launches behind it)
  *   RCFM_OPT_PHASE_LINK   the tuner hands the demodulator angle(x) / pi as float32 (0: complex64 samples, as
- *                         tuner.py:161 returns them) */
+ *                         tuner.py:161 returns them)
+ *   RCFM_OPT_SSB_DIRECT   rcfm_pipeline_run computes USB / LSB audio straight from the tuner's loaded spectrum: one
+ *                         length-A inverse FFT per channel pair, no channel samples (0: the tuner's inverse FFT hands
+ *                         over complex64 samples and the demodulator's own route from samples runs, as rcfm_demod_run) */
 enum { RCFM_OPT_LDS_CHAIN = 1, RCFM_OPT_FUSED_TILES = 2, RCFM_OPT_PHASE_LINK = 3, RCFM_OPT_PILOT_CHAIN = 6, RCFM_OPT_DECIM_TILE = 7,
-       RCFM_OPT_LDS_DEEMPH = 8, RCFM_OPT_PILOT_BLOCKED = 9 };
+       RCFM_OPT_LDS_DEEMPH = 8, RCFM_OPT_PILOT_BLOCKED = 9, RCFM_OPT_SSB_DIRECT = 11 };
 /* (rcfm_demod_set_option itself is declared in rcfm.h.)
  * Reads an option back.  RCFM_OPT_PILOT_BLOCKED reads the EFFECTIVE value: 1 only when the switch is on AND this handle's
  * geometry has the layout and the three-launch pilot chain that reads it (what a test needs to know that it compared two

@@ -80,6 +80,7 @@ enum Stage : int {
     ST_LDS_CHAIN,       // T2 + F1 + F2 of narrow FM / MFM channels in one kernel (lds_chain.h)
     ST_ENVELOPE,        // A1  |x| of AM channels (when the tuner did not store it)
     ST_AM_TAIL,         // A2  AM carrier normalisation and clip
+    ST_SSB_TAIL,        // S2  SSB RMS normalisation and clip
     ST_COUNT
 };
 

@@ -1,5 +1,5 @@
-// The demodulator handle (rcfm_demod_*): the per-chunk kernel chains of FM / MFM / WBFM / AM.run, one method per route
-// a chunk can take, and rcfm_pipeline_run, which joins a tuner to a demodulator.
+// The demodulator handle (rcfm_demod_*): the per-chunk kernel chains of FM / MFM / WBFM / AM / USB / LSB.run, one method
+// per route a chunk can take, and rcfm_pipeline_run, which joins a tuner to a demodulator.
 
 #include <cmath>
 #include <cstring>
@@ -8,7 +8,7 @@
 
 using namespace rcfm;
 
-// The per-chunk kernel chains of FM / MFM / WBFM / AM.run.
+// The per-chunk kernel chains of FM / MFM / WBFM / AM / USB / LSB.run.
 struct rcfm_demod_s {
     Arena* arena = arena_enter_handle();   // rcfm_arena_bind at creation
     ~rcfm_demod_s() {
@@ -67,6 +67,7 @@ struct rcfm_demod_s {
     bool opt_pilot_blocked = true;   // m, p between the pilot stage and the pilot chain in the tile-blocked layout
     bool opt_phase_link = true;
     bool opt_lds_deemph = true;      // MFM's de-emphasis inside the LDS chain
+    bool opt_ssb_direct = true;      // USB / LSB in rcfm_pipeline_run: audio straight from the tuner's spectrum
     int opt_narrow = kNarrowDefault;   // RCFM_OPT_NARROW_TILES
     // RCFM_OPT_GRAPH: one channel per call (the reference's per-channel demodulator.run, tests/benchmark.py:29-31) is ten
     // launches of a few microseconds each: launch-bound.  The second call with the same pointers captures the chain
@@ -108,13 +109,25 @@ struct rcfm_demod_s {
         return A % (2 * n1) == 0 && A / n1 >= 16 && fft_plan_describe(A, &pa, 0, fa, 2);
     }
 
-    // MFM and WBFM carry de-emphasis state from buffer to buffer; FM and AM carry none.
+    // MFM and WBFM carry de-emphasis state from buffer to buffer; FM, AM, USB and LSB carry none.
     bool stateful() const { return kind == RCFM_MFM || kind == RCFM_WBFM; }
+    bool ssb() const { return kind == RCFM_USB || kind == RCFM_LSB; }
 
     void alloc() {
         const size_t c = (size_t)chunk;
         tiles = fir_tiles(A);
 
+        if (ssb()) {
+            // linear from spectrum to audio: no real-signal buffers.  The engine serves each length it has a plan for
+            // (the spectrum-direct route needs A only); route 2 takes rocFFT for both transforms unless both are there.
+            FftPlanDesc probe;
+            if (use_engine() && fft_plan_describe(A, &probe)) {
+                eng_A = std::make_unique<FftEngine>(A);
+                buf_TA.reset(((c + 1) / 2) * eng_A->tmp_stride() * sizeof(float2));
+            }
+            if (eng_A && fft_plan_describe(B, &probe)) eng_B = std::make_unique<FftEngine>(B);
+            return;
+        }
         if (kind == RCFM_WBFM) {
             buf_P.reset(c * (B / 2 + 1) * sizeof(float2));
             buf_Z.reset(c * B * sizeof(float2));      // analytic pilot, then the packed L/R signal
@@ -275,7 +288,10 @@ struct rcfm_demod_s {
 
     // Does run_chunk take the samples' phases (theta = angle(x) / pi, float32 [cnt][B]) instead of iq?
     // AM never: its chain starts from |x|, which the phases do not hold (the tuner stores the envelope for it instead).
-    bool phase_capable() const { return eng_B != nullptr && kind != RCFM_AM && (kind != RCFM_WBFM || B % 4 == 0); }
+    // USB / LSB never either: they need the samples' amplitudes as much as their phases.
+    bool phase_capable() const {
+        return eng_B != nullptr && kind != RCFM_AM && !ssb() && (kind != RCFM_WBFM || B % 4 == 0);
+    }
 
     // One chunk of channels [first, first + cnt) from iq (or the tuner's phases) to audio, by one of the routes below.
     void run_chunk(int first, int cnt, const float2* iq, float* audio, hipStream_t s, const float* theta = nullptr,
@@ -289,6 +305,10 @@ struct rcfm_demod_s {
         }
         if (kind == RCFM_AM) {
             run_am(cnt, iq, audio, s, false);
+            return;
+        }
+        if (ssb()) {
+            run_ssb(cnt, iq, audio, s);
             return;
         }
         // fm.py:60-66  discriminator, then Decimate(B -> A) into the audio (FM) or into v, which mfm.py:63-65 de-emphasises
@@ -328,6 +348,69 @@ struct rcfm_demod_s {
         const bool dc = run_real(cnt, audio, s, nullptr, PhaseRows{});
         StageTimer tm(ST_AM_TAIL, s);
         launch_am_tail(audio, A, cnt, dc ? buf_dc.as<float2>() : nullptr, s);
+    }
+
+    // USB / LSB (include/rcfm.h): where the sideband's spectrum comes from, for fused_ssb_ifft.
+    SsbSource ssb_source(const float2* X, const int32_t* base32, int64_t N) const {
+        return SsbSource{X, base32, N, B, kind == RCFM_LSB, geom.wr.as<float>(), geom.nyq_factor};
+    }
+
+    void ssb_tail(int cnt, float* audio, hipStream_t s) {
+        StageTimer tm(ST_SSB_TAIL, s);
+        launch_ssb_tail(audio, A, cnt, RCFM_SSB_LEVEL, s);
+    }
+
+    // USB / LSB, route 1 (rcfm_pipeline_run only): the audio of channels [first, first + cnt) straight from the tuner's
+    // loaded spectrum -- IFFT_A of bins picked and weighted on the load, two channels per transform, then the tail.
+    // Neither the tuner's IFFT_B nor any B-point transform or resample of this handle runs.
+    bool ssb_direct_ok(rcfm_tuner_s& t, int first) const {
+        return ssb() && opt_ssb_direct && eng_A && A <= B && t.fast_gather_ok(first);
+    }
+    void run_ssb_direct(rcfm_tuner_s& t, int first, int cnt, float* audio, hipStream_t s) {
+        t.require_readable(first, cnt, "rcfm_pipeline_run", RCFM_ERR_SIZE, "input_sig size and input_size mismatch");
+        {
+            StageTimer tm(ST_IFFT_A, s);
+            TILE_CALL(narrow_launch(*eng_A, (cnt + 1) / 2, opt_narrow), fused_ssb_ifft, *eng_A,
+                      ssb_source(t.spectrum(), t.base_dev.as<int32_t>() + first, t.n), audio, buf_TA.as<float2>(), cnt, s);
+        }
+        ssb_tail(cnt, audio, s);
+    }
+
+    // USB / LSB, route 2, from channel samples: FFT_B keeping |k| <= min(A, B) / 2, then the same inverse transform
+    // reading those spectra; lengths outside the engine take rocFFT around a select-and-weight kernel.
+    void run_ssb(int cnt, const float2* iq, float* audio, hipStream_t s) {
+        if (eng_B && eng_A) {
+            buf_Z.reserve((size_t)chunk * B * sizeof(float2));
+            buf_T.reserve((size_t)chunk * eng_B->tmp_stride() * sizeof(float2));
+            {
+                StageTimer tm(ST_FFT_B, s);
+                TILE_CALL(narrow(cnt), fused_fft_pruned, *eng_B, iq, buf_Z.as<float2>(), buf_T.as<float2>(), cnt,
+                          std::min(A, B) / 2, s);
+            }
+            StageTimer tm(ST_IFFT_A, s);
+            TILE_CALL(narrow_launch(*eng_A, (cnt + 1) / 2, opt_narrow), fused_ssb_ifft, *eng_A,
+                      ssb_source(buf_Z.as<float2>(), nullptr, B), audio, buf_TA.as<float2>(), cnt, s);
+        } else {
+            size_t need = 0;
+            FftPlan& f1 = c2c_fwd_B.get(FftKind::C2C_FORWARD, B, cnt, false, need);
+            FftPlan& f2 = c2r_A.get(FftKind::C2R, A, cnt, false, need);
+            work.reserve(need);
+            buf_Z.reserve((size_t)chunk * B * sizeof(float2));
+            buf_V.reserve((size_t)chunk * (A / 2 + 1) * sizeof(float2));
+            {
+                StageTimer tm(ST_FFT_B, s);
+                f1.exec(const_cast<float2*>(iq), buf_Z.get(), work.get(), s);   // out of place: iq is only read
+            }
+            {
+                StageTimer tm(ST_AUDIO_SPECTRUM, s);
+                launch_ssb_select(buf_Z.as<float2>(), B, buf_V.as<float2>(), A, cnt, geom.wr.as<float>(),
+                                  (int)std::min<int64_t>(A / 2, (B - 1) / 2), (A % 2 == 0 && A < B) ? A / 2 : -1,
+                                  geom.nyq_factor, geom.scale, kind == RCFM_LSB, s);
+            }
+            StageTimer tm(ST_IFFT_A, s);
+            f2.exec(buf_V.get(), audio, work.get(), s);
+        }
+        ssb_tail(cnt, audio, s);
     }
 
     // wbfm.py:77-80  FM(B->B) and the pilot band-pass
@@ -611,7 +694,8 @@ extern "C" {
 int rcfm_demod_create(int kind, int C, int B, int A, double tau, int chunk, rcfm_demod_t* out) {
     return guarded([&] {
         RC_REQUIRE(out != nullptr, RCFM_ERR_ARG, "out is NULL");
-        RC_REQUIRE(kind >= RCFM_FM && kind <= RCFM_AM, RCFM_ERR_ARG, "unknown demodulator kind");
+        RC_REQUIRE((kind >= RCFM_FM && kind <= RCFM_AM) || kind == RCFM_USB || kind == RCFM_LSB, RCFM_ERR_ARG,
+                   "unknown demodulator kind");
         RC_REQUIRE(C >= 1 && B >= 2 && A >= 1, RCFM_ERR_ARG, "bad demodulator size");
         auto d = std::make_unique<rcfm_demod_s>();
         ArenaScope scope(d->arena);
@@ -706,7 +790,7 @@ int rcfm_demod_bind_state(rcfm_demod_t single, rcfm_demod_t batched, int index, 
                        single->tau == batched->tau,
                    RCFM_ERR_ARG, "bind_state needs demodulators of one class, audio rate and time constant");
         require_channels(index, single->C, batched->C);
-        if (!single->stateful()) return;   // fm.py carries no state, nor does AM
+        if (!single->stateful()) return;   // fm.py carries no state, nor do AM, USB and LSB
         const size_t per = (size_t)single->C * single->ch * 50;
         const size_t slot = batched->state_off + (size_t)index * single->ch * 50;
         float* dst = batched->state_at(index);
@@ -735,6 +819,7 @@ int rcfm_demod_set_option(rcfm_demod_t d, int option, int value) {
             case RCFM_OPT_PILOT_BLOCKED: d->opt_pilot_blocked = value != 0; break;
             case RCFM_OPT_LDS_DEEMPH: d->opt_lds_deemph = value != 0; break;
             case RCFM_OPT_PHASE_LINK: d->opt_phase_link = value != 0; break;
+            case RCFM_OPT_SSB_DIRECT: d->opt_ssb_direct = value != 0; break;
             case RCFM_OPT_NARROW_TILES:
                 RC_REQUIRE(value >= 0 && value <= 2, RCFM_ERR_ARG, "narrow tiles: 0 never, 1 automatic, 2 always");
                 d->opt_narrow = value;
@@ -766,6 +851,7 @@ int rcfm_demod_get_option(rcfm_demod_t d, int option, int* value) {
                 break;
             case RCFM_OPT_LDS_DEEMPH: *value = d->opt_lds_deemph; break;
             case RCFM_OPT_PHASE_LINK: *value = d->opt_phase_link; break;
+            case RCFM_OPT_SSB_DIRECT: *value = d->opt_ssb_direct; break;
             case RCFM_OPT_NARROW_TILES: *value = d->opt_narrow; break;
             case RCFM_OPT_STATE_FENCE: *value = d->state_buf->armed; break;
             // 0 = off (or this runtime refused the capture), 1 = on, 1 + k = on and k captured chains are being replayed
@@ -803,6 +889,12 @@ int rcfm_pipeline_run(rcfm_tuner_t t, rcfm_demod_t d, int first, int count, void
             if (d->opt_lds_chain && (d->kind == RCFM_FM || d->kind == RCFM_MFM) && lds_chain_supported(d->B, d->A) &&
                 t->fast_gather_ok(c0)) {
                 d->run_lds_chain(*t, c0, cnt, out_c, s);
+                continue;
+            }
+            // USB / LSB: everything is linear and the wideband spectrum is already loaded -- no channel samples at all.
+            // RCFM_OPT_SSB_DIRECT = 0 (or a geometry the fast gather refuses): complex hand-over + route 2 below.
+            if (d->ssb_direct_ok(*t, c0)) {
+                d->run_ssb_direct(*t, c0, cnt, out_c, s);
                 continue;
             }
             // AM's counterpart of the phase link: the tuner's last pass stores |x| (float32, contiguous) straight into

@@ -31,6 +31,22 @@ struct PhaseRows {
     int64_t channel_stride(int64_t n) const { return row ? (n / row) * (int64_t)pitch : n; }
 };
 
+// Where fused_ssb_ifft takes the spectrum of a single-sideband channel from (RCFM_USB / RCFM_LSB, include/rcfm.h).
+//   base32 != nullptr  the Tuner's loaded wideband spectrum, addressed like TunerGather's fast form: X = bin 0 of the
+//                      haloed spectrum, bin q of channel c (|q| <= A/2 <= halo) is X[base32[c] + q]; the Tuner's Hann
+//                      weight is applied here, N = the wideband length;
+//   base32 == nullptr  X [count][B] = FFT_B of the channel samples, of which bins |k| <= min(A, B) / 2 are valid
+//                      (fused_fft_pruned).
+struct SsbSource {
+    const float2* X;
+    const int32_t* base32;
+    int64_t N;
+    int B;
+    bool lower;            // LSB: bin -k, conjugated, in the place of bin +k
+    const float* wr;       // Decimate(B -> A)'s folded Hamming weight (ResampleGeom::wr)
+    float nyq_factor;      // ... and its Nyquist factor (applies when A is even and A < B)
+};
+
 // fused_real_pair_fft / StorePruned: keep only bins 0 .. n/2 (all the packed Hilbert chain reads)
 constexpr int kKeepLowerHalf = -2;
 

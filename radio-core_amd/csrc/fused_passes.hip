@@ -881,5 +881,103 @@ void fused_ifft_real_out(const FftEngine& e, const float2* Y, float* y, float2* 
     fftk::launch_fft_pass<kRowsOnly>(e.pass_dev(np - 1, e.tmp_stride(), n), count, ldl, stl, s);
 }
 
+// SSB (fused_passes_decl.h, fused_ssb_ifft): point k of the packed Hermitian pair Z = Y0 + j Y1 of channels 2P, 2P + 1.
+// DIRECT: from the haloed wideband spectrum (32-bit bases, the 4-term Hann series of LoadTunerGatherFast -- the caller
+// checks the same preconditions); else from pruned channel spectra [count][B].
+template <bool DIRECT>
+struct LoadSsbPairT {
+    static constexpr int kFetches = 3;
+    const float2* X;
+    const int32_t* base;    // DIRECT: per channel (N - roll) mod N
+    const float* wr;        // folded Hamming weight, at least kmax + 1 entries
+    float two_pi_over_n, delta;
+    float c0, c1, c2, c3;   // 0.5 + 0.5 cos(th) = c0 + t c1 + t^2 c2 + t^3 c3, t = th^2
+    int B, A, count;
+    int kmax;               // bins 1 .. kmax of the sideband survive: min(A / 2, (B - 1) / 2)
+    int nyq_bin;            // A / 2 when A is even and A < B (Decimate's Nyquist rule), else -1
+    float nyq_factor, scale;
+    int lower;
+    int line_stride;
+
+    __device__ __forceinline__ int folded(int k) const { return k > A / 2 ? A - k : k; }
+    __device__ __forceinline__ bool kept(int kk) const { return kk >= 1 && kk <= kmax; }
+    // element of channel c that holds sideband bin kk (bin 0 -- always readable -- for a dropped one)
+    __device__ __forceinline__ float2 bin(int c, int kk) const {
+        const int q = kept(kk) ? (lower ? -kk : kk) : 0;
+        if (DIRECT) return X[base[c] + q];
+        return (X + (int64_t)c * B)[q < 0 ? B + q : q];
+    }
+    __device__ __forceinline__ float2 fetch(const LineId& id, int l, int64_t, unsigned) const {
+        return bin(2 * id.batch, folded(l * line_stride + (int)id.i));
+    }
+    __device__ __forceinline__ float2 fetch2(const LineId& id, int l, int64_t, unsigned) const {
+        const int c1 = 2 * id.batch + 1;
+        return bin(c1 < count ? c1 : c1 - 1, folded(l * line_stride + (int)id.i));
+    }
+    __device__ __forceinline__ float fetch3(const LineId& id, int l, int64_t, unsigned) const {
+        const int kk = folded(l * line_stride + (int)id.i);
+        return wr[kept(kk) ? kk : 0];
+    }
+    __device__ __forceinline__ float2 post(const LineId& id, int l, float2 a, float2 b, float w0) const {
+        const int k = l * line_stride + (int)id.i;
+        const bool mirrored = k > A / 2;
+        const int kk = mirrored ? A - k : k;
+        float w = kept(kk) ? w0 * scale : 0.f;
+        if (DIRECT) {
+            const float th = fmaf((float)(lower ? -kk : kk), two_pi_over_n, delta);
+            const float t = th * th;
+            w *= fmaf(t, fmaf(t, fmaf(t, c3, c2), c1), c0);
+        }
+        if (kk == nyq_bin) w *= nyq_factor;
+        // conj for LSB, conj again for the mirrored half; the Nyquist bin of a real signal is real
+        const float sgn = (kk == nyq_bin) ? 0.f : ((lower != 0) != mirrored ? -w : w);
+        const float w1 = (2 * id.batch + 1 < count) ? 1.f : 0.f;   // an odd last channel rides alone
+        const float2 y0 = make_float2(a.x * w, a.y * sgn);
+        const float2 y1 = make_float2(b.x * w * w1, b.y * sgn * w1);
+        // Z = Y0 + j Y1, handed on with re / im exchanged: inverse transform by the swap identity
+        return make_float2(y0.y + y1.x, y0.x - y1.y);
+    }
+};
+
+void fused_ssb_ifft(const FftEngine& e, const SsbSource& src, float* y, float2* tmp, int count, hipStream_t s) {
+    if (count <= 0) return;
+    const int64_t A = e.desc().n;
+    const int np = e.npass();
+    const int pairs = (count + 1) / 2;
+    const int kmax = (int)std::min<int64_t>(A / 2, (src.B - 1) / 2);
+    const int nyq_bin = (A % 2 == 0 && A < src.B) ? (int)(A / 2) : -1;
+    fftk::StorePlainT<false> st0{tmp, 1.0f};
+    auto first_pass = [&](auto ld) {
+        ld.X = src.X;
+        ld.base = src.base32;
+        ld.wr = src.wr;
+        ld.two_pi_over_n = (float)(6.28318530717958647692 / (double)src.N);
+        ld.delta = (src.N % 2) ? (float)(3.14159265358979323846 / (double)src.N) : 0.f;
+        ld.c0 = 1.f;   // Hann: a0 = 0.5 in LoadTunerGatherFast's series
+        ld.c1 = -0.25f;
+        ld.c2 = (float)(0.5 / 24.0);
+        ld.c3 = (float)(-0.5 / 720.0);
+        ld.B = src.B;
+        ld.A = (int)A;
+        ld.count = count;
+        ld.kmax = kmax;
+        ld.nyq_bin = nyq_bin;
+        ld.nyq_factor = src.nyq_factor;
+        // irfft's 1 / A, Decimate's A / B and -- from the wideband spectrum -- the Tuner's B / N
+        ld.scale = (float)(1.0 / (double)(src.base32 ? src.N : (int64_t)src.B));
+        ld.lower = src.lower ? 1 : 0;
+        ld.line_stride = (int)e.desc().pass[0].in_l;
+        fftk::launch_fft_pass<kStridedOnly>(e.pass_dev(0, 0, e.tmp_stride()), pairs, ld, st0, s);
+    };
+    if (src.base32 != nullptr)
+        first_pass(LoadSsbPairT<true>{});
+    else
+        first_pass(LoadSsbPairT<false>{});
+    middle_passes(e, 1, np - 2, tmp, pairs, s);
+    fftk::LoadPlainT<false> ldl{tmp};
+    StoreRealImagSplit stl{y, (int)A, count};
+    fftk::launch_fft_pass<kRowsOnly>(e.pass_dev(np - 1, e.tmp_stride(), A), pairs, ldl, stl, s);
+}
+
 RCFM_NS_CLOSE
 }  // namespace rcfm

@@ -104,5 +104,14 @@ void fused_ifft_real_out(const FftEngine& e, const float2* Y, float* y, float2* 
                          hipStream_t s);
 
 
+// SSB: audio-rate inverse FFT of single-sideband channels straight from a spectrum (fused_passes.h, SsbSource): the load
+// of e's first pass picks bins 1 .. min(A / 2, (B - 1) / 2) of one sideband, weights them (Hann of the Tuner when the
+// source is the wideband spectrum, folded Hamming and Nyquist rule of Decimate(B -> A)) and builds the Hermitian spectra
+// of TWO channels per complex transform, Z[k] = Y0[k] + j Y1[k], Z[A - k] = conj Y0[k] + j conj Y1[k]; the last pass
+// stores the real part as channel 2P and the imaginary part as channel 2P + 1 of y [count][A] float32 (an odd last
+// channel rides alone).  y = Decimate(B -> A)(Re(ifft(H fft(x)))) without x, its B-point transforms or a resample pass.
+// tmp: ceil(count / 2) * e.tmp_stride() elements.
+void fused_ssb_ifft(const FftEngine& e, const SsbSource& src, float* y, float2* tmp, int count, hipStream_t s);
+
 RCFM_DECL_NS_CLOSE
 }  // namespace rcfm

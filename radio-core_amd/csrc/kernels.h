@@ -124,4 +124,13 @@ void launch_envelope(const float2* iq, float* e, int64_t n, hipStream_t stream);
 // resampled spectrum (= the mean of y); else every channel reduces its own y first.
 void launch_am_tail(float* y, int64_t n, int batch, const float2* dc, hipStream_t stream);
 
+// SSB (RCFM_USB / RCFM_LSB) between rocFFT's transforms: full spectra X [batch][n] of the channel samples -> half
+// spectra Y [batch][m / 2 + 1] of the resampled sideband signal (bins 1 .. kmax of the upper, or mirrored lower, half;
+// wr, nyq_bin / nyq_factor and scale as in launch_spectrum_r2c).
+void launch_ssb_select(const float2* X, int64_t n, float2* Y, int64_t m, int batch, const float* wr, int kmax,
+                       int nyq_bin, float nyq_factor, float scale, bool lower, hipStream_t stream);
+// SSB's tail, in place on y [batch][n]: y = clip(level y / g, +-0.999) with g = the channel's RMS, zeros when !(g > 0).
+// One workgroup per channel and a fixed summation order: bit-identical from run to run.
+void launch_ssb_tail(float* y, int64_t n, int batch, float level, hipStream_t stream);
+
 }  // namespace rcfm

@@ -919,6 +919,68 @@ __global__ __launch_bounds__(kThreads) void k_am_tail(float* __restrict__ y, int
     }
 }
 
+// SSB (RCFM_USB / RCFM_LSB) between rocFFT's transforms: X [batch][n] = FFT_n of the channel samples -> the half
+// spectrum Y [batch][m / 2 + 1] of the resampled sideband signal.  Bin k of s = Re(ifft(H X)) is X[k] (USB) or
+// conj X[n - k] (LSB) for 1 <= k <= kmax = min(m / 2, (n - 1) / 2) and zero elsewhere (DC and the bin n / 2 are dropped);
+// then Decimate's folded Hamming weight wr, its Nyquist rule at k = nyq_bin (m even, m < n; else -1), and `scale`.
+__global__ __launch_bounds__(kThreads) void k_ssb_select(const float2* __restrict__ X, int64_t n, float2* __restrict__ Y,
+                                                         int64_t m, const float* __restrict__ wr, int kmax, int nyq_bin,
+                                                         float nyq_factor, float scale, int lower) {
+    const int c = blockIdx.y;
+    const int64_t mh = m / 2 + 1;
+    const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (k >= mh) return;
+    float2 y = make_float2(0.f, 0.f);
+    if (k >= 1 && k <= kmax) {
+        y = cscale(X[(int64_t)c * n + (lower ? n - k : k)], wr[k] * scale);
+        if (lower) y.y = -y.y;
+        if (k == nyq_bin) y = make_float2(y.x * nyq_factor, 0.f);   // a real inverse transform never sees its imaginary part
+    }
+    Y[(int64_t)c * mh + k] = y;
+}
+
+// SSB's tail on channel blockIdx.x of y [batch][n], in place: g = sqrt(mean(y^2)), y = clip(level y / g, +-0.999), zeros
+// when !(g > 0).  ONE workgroup per channel, so the sum has one order whatever the launch: thread t adds samples
+// t, t + kThreads, ... (VEC: quads) in float64, then the waves' shuffle tree, then the four wave sums in order -- audio
+// is bit-identical from run to run and under graph replay.  The second sweep re-reads what the first left in cache.
+// VEC (n % 4 == 0 and y 16-byte aligned): 16-byte accesses.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_ssb_tail(float* __restrict__ y, int64_t n, float level) {
+    __shared__ double red[kThreads / 64];
+    const int tid = threadIdx.x;
+    float* yc = y + (int64_t)blockIdx.x * n;
+    double acc = 0.0;
+    if (VEC) {
+        for (int64_t i = 4 * (int64_t)tid; i < n; i += 4 * kThreads) {
+            const float4 v = *reinterpret_cast<const float4*>(yc + i);
+            acc += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += kThreads) acc += (double)yc[i] * yc[i];
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    double tot = 0.0;
+    for (int w = 0; w < kThreads / 64; ++w) tot += red[w];
+    const float g = (float)sqrt(tot / (double)n);
+    const bool live = g > 0.f;   // false for 0 and NaN: a silent channel gives zeros
+    const float gain = live ? level / g : 0.f;
+    auto tail = [&](float v) {
+        if (!live) return 0.f;
+        v *= gain;
+        return (v < -0.999f) ? -0.999f : ((v > 0.999f) ? 0.999f : v);
+    };
+    if (VEC) {
+        for (int64_t i = 4 * (int64_t)tid; i < n; i += 4 * kThreads) {
+            const float4 v = *reinterpret_cast<const float4*>(yc + i);
+            *reinterpret_cast<float4*>(yc + i) = make_float4(tail(v.x), tail(v.y), tail(v.z), tail(v.w));
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += kThreads) yc[i] = tail(yc[i]);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1130,6 +1192,23 @@ void launch_am_tail(float* y, int64_t n, int batch, const float2* dc, hipStream_
         hipLaunchKernelGGL(k_am_tail<true>, grid, dim3(kThreads), 0, stream, y, n, dc);
     else
         hipLaunchKernelGGL(k_am_tail<false>, grid, dim3(kThreads), 0, stream, y, n, dc);
+    RC_LAUNCH_CHECK();
+}
+
+void launch_ssb_select(const float2* X, int64_t n, float2* Y, int64_t m, int batch, const float* wr, int kmax,
+                       int nyq_bin, float nyq_factor, float scale, bool lower, hipStream_t stream) {
+    if (batch <= 0) return;
+    hipLaunchKernelGGL(k_ssb_select, grid2(m / 2 + 1, kThreads, batch), dim3(kThreads), 0, stream, X, n, Y, m, wr, kmax,
+                       nyq_bin, nyq_factor, scale, lower ? 1 : 0);
+    RC_LAUNCH_CHECK();
+}
+
+void launch_ssb_tail(float* y, int64_t n, int batch, float level, hipStream_t stream) {
+    if (batch <= 0 || n <= 0) return;
+    if (n % 4 == 0 && (uintptr_t)y % 16 == 0)
+        hipLaunchKernelGGL(k_ssb_tail<true>, dim3((unsigned)batch), dim3(kThreads), 0, stream, y, n, level);
+    else
+        hipLaunchKernelGGL(k_ssb_tail<false>, dim3((unsigned)batch), dim3(kThreads), 0, stream, y, n, level);
     RC_LAUNCH_CHECK();
 }
 

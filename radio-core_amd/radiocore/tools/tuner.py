@@ -15,8 +15,9 @@ from radiocore._internal import Injector, hip
 
 __all__ = ["Tuner", "Channel"]
 
-_KINDS = {"FM": hip.RCFM_FM, "MFM": hip.RCFM_MFM, "WBFM": hip.RCFM_WBFM, "AM": hip.RCFM_AM}
-_STATELESS = (hip.RCFM_FM, hip.RCFM_AM)    # kinds without de-emphasis state: nothing to bind or fence
+_KINDS = {"FM": hip.RCFM_FM, "MFM": hip.RCFM_MFM, "WBFM": hip.RCFM_WBFM, "AM": hip.RCFM_AM,
+          "USB": hip.RCFM_USB, "LSB": hip.RCFM_LSB}
+_STATELESS = (hip.RCFM_FM, hip.RCFM_AM, hip.RCFM_USB, hip.RCFM_LSB)    # kinds without de-emphasis state: nothing to bind or fence
 
 
 @dataclass
@@ -355,7 +356,7 @@ class Tuner(Injector):
         blocks = []
         for i, n, kind, B, A, tau in groups:
             if kind is None:
-                raise ValueError("run_each needs an FM, MFM, WBFM or AM demodulator on every channel")
+                raise ValueError("run_each needs an FM, MFM, WBFM, AM, USB or LSB demodulator on every channel")
             ch = 2 if kind == hip.RCFM_WBFM else 1
             audio = hip.empty((n, A, ch), self._torch.float32)
             hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, 0), i, n,
@@ -383,20 +384,21 @@ class Tuner(Injector):
         for h in self._batched.values():
             hip.check(self._lib.rcfm_demod_reset_state(h.value, hip.stream()))
 
-    def set_kernel_options(self, lds_chain=True, fused_tiles=True, phase_link=True, narrow_tiles=1):
+    def set_kernel_options(self, lds_chain=True, fused_tiles=True, phase_link=True, narrow_tiles=1, ssb_direct=True):
         """Which forms of the kernel chain run_all / run_each may use (rcfm_demod_set_option; no reference
         counterpart).  The audio does not depend on them beyond float32 rounding: switching all three off gives a
         second evaluation of the same path that shares no kernel schedule with the default one, which is what the
         full-size parity tests compare against.  narrow_tiles: 0 = tile kernels with 16 lines per tile always, 1 = 8 lines
-        when a launch has fewer than two tiles per CU (the default), 2 = always 8.  Takes effect with the next run_all /
-        run_each."""
-        self._kernel_options = (bool(lds_chain), bool(fused_tiles), bool(phase_link), int(narrow_tiles))
+        when a launch has fewer than two tiles per CU (the default), 2 = always 8.  ssb_direct: USB / LSB audio straight
+        from the loaded spectrum (False: through channel samples, RCFM_OPT_SSB_DIRECT).  Takes effect with the next
+        run_all / run_each."""
+        self._kernel_options = (bool(lds_chain), bool(fused_tiles), bool(phase_link), int(narrow_tiles), bool(ssb_direct))
 
     def _batched_demod(self, kind, B, A, tau, chunk):
         # one handle per geometry, sized for all channels: rcfm_pipeline_run addresses the channels of tuner and
         # demodulator by the same index, so the per-channel state survives regrouping
-        opts = getattr(self, "_kernel_options", (True, True, True, 1))
-        key = (kind, len(self._bounds), B, A, tau, int(chunk)) + ((opts,) if opts != (True, True, True, 1) else ())
+        opts = getattr(self, "_kernel_options", (True, True, True, 1, True))
+        key = (kind, len(self._bounds), B, A, tau, int(chunk)) + ((opts,) if opts != (True, True, True, 1, True) else ())
         if key not in self._batched:
             h = ctypes.c_void_p()
             with hip.bound(self._arena):
@@ -405,6 +407,8 @@ class Tuner(Injector):
             for opt, on in zip((hip.RCFM_OPT_LDS_CHAIN, hip.RCFM_OPT_FUSED_TILES, hip.RCFM_OPT_PHASE_LINK), opts[:3]):
                 if not on:
                     hip.check(self._lib.rcfm_demod_set_option(h, opt, 0))
+            if not opts[4]:
+                hip.check(self._lib.rcfm_demod_set_option(h, hip.RCFM_OPT_SSB_DIRECT, 0))
             if opts[3] != 1:   # (rcfm_pipeline_run hands the same setting to the tuner's inverse FFT of each chunk)
                 hip.check(self._lib.rcfm_demod_set_option(h, hip.RCFM_OPT_NARROW_TILES, opts[3]))
             self._bind_states(key, self._batched[key])
@@ -421,7 +425,7 @@ class Tuner(Injector):
         what it has carried so far), and further batched handles of the same geometry (another `chunk`) share the
         first one's buffer.  Mixing ``ch.demodulator.run(tuner.run(i))`` and ``run_all()`` across buffers then gives
         what the reference's loop gives.  O(C) Python, once per change of the channel list; a demodulator whose own
-        librcfm handle does not exist yet (it is created on first use) binds when it does; FM and AM carry no state."""
+        librcfm handle does not exist yet (it is created on first use) binds when it does; FM, AM, USB and LSB carry no state."""
         kind, C, B, A, tau = key[:5]
         self._bound_version[key] = self._version
         if kind in _STATELESS:
