@@ -98,21 +98,6 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
     const int64_t out_base = (int64_t)id.batch * d2.out_batch + i0;
     const unsigned in_i = (unsigned)p1.in_i, out_k = (unsigned)p2.out_k;
 
-    auto kbase = [](int g) -> int {
-        if constexpr (S == 2) {
-            return g;
-        } else if constexpr (S == 3) {
-            constexpr int w1 = L / (R0 * RL);
-            const int q1 = g / w1, q2 = g - q1 * w1;
-            return q1 + R0 * q2;
-        } else {
-            constexpr int w1 = L / (R0 * RL), w2 = L / (R0 * R1 * RL);
-            const int q1 = g / w1, r1 = g - q1 * w1;
-            const int q2 = r1 / w2, q3 = r1 - q2 * w2;
-            return q1 + R0 * (q2 + R1 * q3);
-        }
-    };
-
     // ---- the long transform: exactly k_fft_tile2_decim's ---------------------------------------------
     float2 v[nld];
 #pragma unroll
@@ -161,7 +146,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
     for (int it = 0; it < nitL; ++it) {
         const int g = rg + RG * it;
         if ((rowsL % RG == 0) || g < rowsL) {
-            const int kb = kbase(g);
+            const int kb = last_stage_base<L, R0, R1, RL, S>(g);
 #pragma unroll
             for (int q = 0; q < RL; ++q) {
                 const int k = kb + (L / RL) * q;

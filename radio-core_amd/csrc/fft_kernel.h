@@ -628,6 +628,26 @@ constexpr bool big_tile_pair(int L) { return L > kFftMaxL; }
 // cfg5 (400 . 625 . 400 wideband plan) 2.095 -> 2.067 ms, same-box alternation.
 constexpr bool triple_tile(int L) { return L == 400; }
 
+// Output index of slot 0 of last-stage block g, shared by every tile kernel (and fft_decim_rt.h).  The last stage (block
+// length RL, no stage twiddle) leaves its results in digit-reversed slots: block g holds outputs k = last_stage_base(g) +
+// (L / RL) q', q' < RL.  g's digits are q_1 .. q_{S-1} with weights L/(r_1 RL), L/(r_1 r_2 RL), ...; the base is
+// q_1 + r_1 q_2 + r_1 r_2 q_3.  (S = number of stages, RL = last radix.)
+template <int L, int R0, int R1, int RL, int S>
+__device__ __forceinline__ int last_stage_base(int g) {
+    if constexpr (S == 2) {
+        return g;
+    } else if constexpr (S == 3) {
+        constexpr int w1 = L / (R0 * RL);
+        const int q1 = g / w1, q2 = g - q1 * w1;
+        return q1 + R0 * q2;
+    } else {
+        constexpr int w1 = L / (R0 * RL), w2 = L / (R0 * R1 * RL);
+        const int q1 = g / w1, r1 = g - q1 * w1;
+        const int q2 = r1 / w2, q3 = r1 - q2 * w2;
+        return q1 + R0 * (q2 + R1 * q3);
+    }
+}
+
 // LoadOp contract:  fetch(id, l, tile_base, off) returns element tile_base + off of the input
 //                   (tile_base is workgroup-uniform, off a 32-bit per-lane offset) and does NO
 //                   arithmetic on the value; post(id, l, v) runs when the tile is consumed.
@@ -739,7 +759,8 @@ __global__ __launch_bounds__(T, (big_tile_pair(L) ? 8 : triple_tile(L) ? 6 : T *
         else return 0;
     }();
 
-    // Output index of slot 0 of last-stage block g (see the last stage below).
+    // last_stage_base<L, R0, R1, RL, S>, written out: called as a function (or through a one-line lambda) it changes the
+    // emitted code of the three-stage strided tiles (their index divisions stop being 16-bit).
     constexpr int rowsL = L / RL, nitL = (rowsL + RG - 1) / RG;
     auto kbase = [](int g) -> int {
         if constexpr (S == 2) {
@@ -836,8 +857,7 @@ __global__ __launch_bounds__(T, (big_tile_pair(L) ? 8 : triple_tile(L) ? 6 : T *
     }
 
     // ---- last stage (block length RL, no stage twiddle): LDS -> registers -> memory ---------
-    // Block g holds outputs k = kb(g) + (L / RL) q': g's digits are q_1 .. q_{S-1} with weights
-    // L/(r_1 RL), L/(r_1 r_2 RL), ...; kb = q_1 + r_1 q_2 + r_1 r_2 q_3.
+    // Block g holds outputs k = kb + (L / RL) q', kb = kbase(g) (see last_stage_base).
     // Inter-pass twiddle W_n^(f k), f = this lane's line factor: W_n^(f kb) once per butterfly,
     // then successive powers of D = W_n^(f L / RL) (RL - 1 <= 9 multiplications).
     const unsigned f = (unsigned)(id.o1 * p.tw_o1 + id.o2 * p.tw_o2 + (int64_t)(i0 + w) * p.tw_i);
@@ -922,6 +942,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2(Ff
     const int64_t out_base = (int64_t)id.batch * d2.out_batch + i0;
     const unsigned in_i = (unsigned)p1.in_i, mid_k = (unsigned)p1.out_k, out_k = (unsigned)p2.out_k;
 
+    // last_stage_base<L, R0, R1, RL, S>, written out for the same reason as in k_fft_tile (6 instantiations differ)
     auto kbase = [](int g) -> int {
         if constexpr (S == 2) {
             return g;
@@ -1113,26 +1134,12 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
     const unsigned in_i = (unsigned)p1.in_i, mid_k = blk16 ? 16u : (unsigned)p1.out_k, out_k = (unsigned)p2.out_k;
     const int wc = w < wvalid ? w : 0;
 
-    auto kbase = [](int g) -> int {
-        if constexpr (S == 2) {
-            return g;
-        } else if constexpr (S == 3) {
-            constexpr int w1 = L / (R0 * RL);
-            const int q1 = g / w1, q2 = g - q1 * w1;
-            return q1 + R0 * q2;
-        } else {
-            constexpr int w1 = L / (R0 * RL), w2 = L / (R0 * R1 * RL);
-            const int q1 = g / w1, r1 = g - q1 * w1;
-            const int q2 = r1 / w2, q3 = r1 - q2 * w2;
-            return q1 + R0 * (q2 + R1 * q3);
-        }
-    };
     // Natural-order offset of point (it, q) of this thread = lane part (it) + uniform part (q): the
     // uniform part goes into the scalar base, so a thread holds nitL offsets instead of nitL * RL.
     auto lane_off = [&](int it) -> unsigned {
         int g = rg + RG * it;
         if (rowsL % RG != 0) g = g < rowsL ? g : 0;
-        return (unsigned)kbase(g) * mid_k + (unsigned)wc;
+        return (unsigned)last_stage_base<L, R0, R1, RL, S>(g) * mid_k + (unsigned)wc;
     };
     auto q_off = [&](int q) -> int64_t { return (int64_t)((L / RL) * q) * mid_k; };
 
@@ -1202,7 +1209,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
     for (int it = 0; it < nitL; ++it) {
         const int g = rg + RG * it;
         if ((rowsL % RG == 0) || g < rowsL) {
-            const int kb = kbase(g);
+            const int kb = last_stage_base<L, R0, R1, RL, S>(g);
 #pragma unroll
             for (int q = 0; q < RL; ++q) tile[lds_slot<true>(kb + (L / RL) * q, w)] = u0[it * RL + q];
         }
@@ -1232,7 +1239,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
 #pragma unroll
                 for (int q = 0; q < RL; ++q) x[q] = tile[lds_slot<true>(g * RL + q, w)];
                 dft_p<RL>(x);
-                const int kb = kbase(g);
+                const int kb = last_stage_base<L, R0, R1, RL, S>(g);
                 float2 Tw = big_twiddle(d2, f * (unsigned)kb);
                 if (lane_ok) {
 #pragma unroll
@@ -1260,7 +1267,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
     for (int it = 0; it < nitL; ++it) {
         const int g = rg + RG * it;
         if ((rowsL % RG == 0) || g < rowsL) {
-            const int kb = kbase(g);
+            const int kb = last_stage_base<L, R0, R1, RL, S>(g);
 #pragma unroll
             for (int q = 0; q < RL; ++q) {
                 const int k = kb + (L / RL) * q;
@@ -1313,21 +1320,6 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
     const int64_t in_base = (int64_t)id.batch * d1.in_batch + (int64_t)i0 * p1.in_i;
     const int64_t out_base = (int64_t)id.batch * d2.out_batch + i0;
     const unsigned in_i = (unsigned)p1.in_i, out_k = (unsigned)p2.out_k;
-
-    auto kbase = [](int g) -> int {
-        if constexpr (S == 2) {
-            return g;
-        } else if constexpr (S == 3) {
-            constexpr int w1 = L / (R0 * RL);
-            const int q1 = g / w1, q2 = g - q1 * w1;
-            return q1 + R0 * q2;
-        } else {
-            constexpr int w1 = L / (R0 * RL), w2 = L / (R0 * R1 * RL);
-            const int q1 = g / w1, r1 = g - q1 * w1;
-            const int q2 = r1 / w2, q3 = r1 - q2 * w2;
-            return q1 + R0 * (q2 + R1 * q3);
-        }
-    };
 
     // ---- loads: the tile and the weights of the rows that survive -------------------------------
     float2 v[nld];
@@ -1385,7 +1377,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
     for (int it = 0; it < nitL; ++it) {
         const int g = rg + RG * it;
         if ((rowsL % RG == 0) || g < rowsL) {
-            const int kb = kbase(g);
+            const int kb = last_stage_base<L, R0, R1, RL, S>(g);
 #pragma unroll
             for (int q = 0; q < RL; ++q) {
                 // kb < L / RL: the rows k = kb + (L / RL) q of this q lie in [(L/RL) q, (L/RL)(q + 1)); when that range
