@@ -41,7 +41,8 @@ extern "C" {
 #endif
 
 #define RCFM_VERSION 102 /* 0.1.2: tooling entry points moved to rcfm_tools.h (same symbols), RCFM_OPT_GRAPH;
-                            demodulator kinds RCFM_AM, RCFM_USB, RCFM_LSB (no new entry points) */
+                            demodulator kinds RCFM_AM, RCFM_USB, RCFM_LSB (no new entry points);
+                            rcfm_tuner_levels and rcfm_squelch added (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -148,6 +149,26 @@ int rcfm_tuner_window(rcfm_tuner_t t, int first, int count, int64_t* first_bin, 
 int rcfm_tuner_window_layout(rcfm_tuner_t t, int first, int count, int64_t* halo, int64_t* nbins);
 int rcfm_tuner_attach_window(rcfm_tuner_t t, void* storage, int first, int count);
 int rcfm_tuner_adopt(rcfm_tuner_t t, int first, int count, void* stream);
+/* ---- signal levels and squelch (no reference counterpart) ---------------------------------------------------------
+ * The level of channel c (roll r, bandwidth B <= n) of the loaded spectrum X is the mean power of the samples
+ * rcfm_tuner_run would return for it, taken from the B bins the channel reads, without the inverse FFT (Parseval):
+ *   Y = the channel's length-B spectrum: bins k = 0 .. B/2 and their mirror images, each X[(k - r) mod n] times the
+ *       fftshifted periodic Hann weight; for even B < n (B > 2) the two end bins +-B/2 ADDED before squaring;
+ *   level[c] = sum_k |Y[k]|^2 / n^2 = mean(|rcfm_tuner_run(c)|^2): linear power in the units of the input samples.
+ * The channels of a range may differ in bandwidth.  Readiness as for rcfm_tuner_run: RCFM_ERR_STATE before a load and
+ * for a channel outside the range that was loaded, sharded or attached as a window, RCFM_ERR_INDEX for a bad range.
+ * The sums have a fixed order: bit-identical from run to run and from stream to stream.
+ * level[i] of channels [first, first+count), any mix of bandwidths; power: [count] float32 device */
+int rcfm_tuner_levels(rcfm_tuner_t t, int first, int count, void* power, void* stream);
+/* Squelch, per buffer and stateless (no hysteresis, no hang time): channel i is OPEN iff power[i] >= threshold[i]
+ * (false when either is NaN); threshold: [count] float32 device, in the units of rcfm_tuner_levels.
+ * open[i] = power[i] >= threshold[i]; rows of closed channels of audio [count][floats_per_channel] := 0.
+ * audio may be NULL (mask only); open ([count] uint8 device) may be NULL.
+ * Rows of open channels are neither read nor written.  Queue it behind rcfm_pipeline_run on the same stream: the
+ * demodulators have then run on every channel, so the de-emphasis state of MFM / WBFM advances exactly as without
+ * squelch and a channel that reopens carries the audio it would have carried anyway. */
+int rcfm_squelch(const void* power, const void* threshold, int count, size_t floats_per_channel,
+                 void* audio, void* open, void* stream);
 int rcfm_tuner_destroy(rcfm_tuner_t t);
 
 /* ---- demodulators (radiocore/analog/{fm,mfm,wbfm}.py) --------------------- */

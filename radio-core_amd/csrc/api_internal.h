@@ -81,6 +81,8 @@ enum Stage : int {
     ST_ENVELOPE,        // A1  |x| of AM channels (when the tuner did not store it)
     ST_AM_TAIL,         // A2  AM carrier normalisation and clip
     ST_SSB_TAIL,        // S2  SSB RMS normalisation and clip
+    ST_LEVELS,          // L1  per-channel signal levels from the loaded spectrum (rcfm_tuner_levels)
+    ST_SQUELCH,         // L2  squelch mask and zero fill of closed channels (rcfm_squelch)
     ST_COUNT
 };
 
@@ -198,6 +200,8 @@ struct rcfm_tuner_s {
     std::vector<int32_t> bw;
     rcfm::DeviceBuffer roll_dev;
     rcfm::DeviceBuffer base_dev;   // int32 (n - roll) mod n per channel: start of the channel in the haloed spectrum
+    rcfm::DeviceBuffer bw_dev;     // int32 bandwidth per channel (rcfm_tuner_levels: a range may mix bandwidths)
+    rcfm::DeviceBuffer levels_part;   // rcfm_tuner_levels: float64 [count][segments] sums of channels split over workgroups
     rcfm::DeviceBuffer X;          // [halo | n bins | halo]: the halos repeat the far ends, so a channel's bins
     int64_t halo = 0;              //   base + d, |d| <= B/2 + 1, need no wrap-around (fused_passes.h)
     float2* ext = nullptr;         // rcfm_tuner_attach_spectrum: caller-owned storage of the same layout instead of X
@@ -257,10 +261,13 @@ struct rcfm_tuner_s {
     void adopt(int first, int count, hipStream_t s);
     void window_storage(int first, int count, int64_t* fb, int64_t* nb) const;
     bool fast_gather_ok(int first);
+    bool fast_bins_ok(int32_t B) const;
     bool phase_capable(int first);
     int band_row_length(int first);
     bool band_two_pass(int first);
+    void require_loaded(int first, int count, const char* caller) const;
     void require_readable(int first, int count, const char* caller, int bw_code, const char* bw_msg) const;
+    void levels(int first, int count, float* power, hipStream_t s);
     void run(int first, int count, float2* out, hipStream_t s, float* theta = nullptr, int theta_pitch = 0,
              int narrow_mode = -1, bool envelope = false);
 };

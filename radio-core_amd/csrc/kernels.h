@@ -133,4 +133,22 @@ void launch_ssb_select(const float2* X, int64_t n, float2* Y, int64_t m, int bat
 // One workgroup per channel and a fixed summation order: bit-identical from run to run.
 void launch_ssb_tail(float* y, int64_t n, int batch, float level, hipStream_t stream);
 
+// Per-channel signal level (rcfm_tuner_levels): power[c] = sum_k |Y_c[k]|^2 / N^2 over the B_c bins channel c reads from
+// the wideband spectrum X (bin 0 of it), Y_c as launch_spectrum_c2c with the Hann weight builds it (NYQ_DOWN merge
+// included) -- by Parseval the mean |x|^2 of the channel's samples, without the inverse FFT.  bw [count]: B_c <= N;
+// the channels may differ in bandwidth.
+//   base != nullptr (fast form): X is haloed, the run of channel c is X[base[c] - (B_c - 1) / 2 .. base[c] + B_c / 2]
+//     with no wrap-around, read 16 bytes per lane; the window is the 4-term series of the tuner's fast gather.
+//   base == nullptr (general form): bin (d - roll[c]) mod N per element, 64-bit, library cosine.
+// A channel is split into level_segments(B_c) workgroups, a function of B_c alone; part ([count][max segments] float64,
+// needed when any channel has more than one) receives their sums and a finishing launch adds them in segment order:
+// bit-identical from run to run.
+int level_segments(int64_t B);
+void launch_channel_levels(const float2* X, int64_t N, const int32_t* base, const int64_t* roll, const int32_t* bw,
+                           int count, int max_segments, double* part, float* power, hipStream_t stream);
+// Squelch (rcfm_squelch): open[c] = power[c] >= threshold[c] (false for NaN), one byte per channel (open may be null);
+// rows of closed channels of audio [count][row] float32 (may be null) := 0, rows of open channels untouched.
+void launch_squelch(const float* power, const float* threshold, int count, size_t row, float* audio, uint8_t* open,
+                    hipStream_t stream);
+
 }  // namespace rcfm

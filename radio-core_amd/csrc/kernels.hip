@@ -981,6 +981,156 @@ __global__ __launch_bounds__(kThreads) void k_ssb_tail(float* __restrict__ y, in
     }
 }
 
+// ---------------------------------------------------------------------------
+// Signal levels and squelch (rcfm_tuner_levels, rcfm_squelch)
+// ---------------------------------------------------------------------------
+
+constexpr int kLevelSegBins = 8192;   // bins per workgroup of k_channel_levels (64 KB of spectrum)
+constexpr int kLevelMaxSegs = 64;
+
+// The fftshifted periodic Hann weight at signed bin offset d of the channel centre, th = 2 pi d / N (+ pi / N for odd N):
+// SERIES: 0.5 + 0.5 cos(th) as the 4-term series of the tuner's fast gather (|th| < 0.25); else the library cosine.
+template <bool SERIES>
+__device__ __forceinline__ float level_window(int d, float two_pi_over_n, float delta) {
+    const float th = fmaf((float)d, two_pi_over_n, delta);
+    if constexpr (SERIES) {
+        const float t = th * th;
+        return fmaf(t, fmaf(t, fmaf(t, -0.5f / 720.f, 0.5f / 24.f), -0.25f), 1.f);
+    } else {
+        return 0.5f + 0.5f * cosf(th);
+    }
+}
+
+// |x w|^2 in float64 from the float32 products the tuner's gather forms.
+__device__ __forceinline__ double level_term(float re, float im, float w) {
+    const float a = re * w, b = im * w;
+    return (double)a * a + (double)b * b;
+}
+
+// Level of channel blockIdx.x, segment blockIdx.y (kernels.h, launch_channel_levels).  The channel's B bins sit at signed
+// offsets d = -(B - 1) / 2 .. B / 2 of its centre; NYQ_DOWN (B even, 2 < B < N): bin +B/2 also receives bin -B/2 BEFORE
+// squaring, so the run that the workgroups share stops one short (d < B / 2) and thread 0 of segment 0 adds that one term.
+// FAST: the run is X[base - (B - 1) / 2 ...] of the haloed spectrum.  Its start is 8- or 16-byte aligned (the parity of
+// base differs per channel): thread 0 of segment 0 takes the head element of a misaligned run and the odd one at the end,
+// everything between is pairs of bins, one 16-byte load per lane, the segments splitting the pairs evenly.
+// !FAST: element e of the run is bin (d - roll) mod N, one 8-byte load per lane.
+// Sums as k_ssb_tail: per-thread strided float64, the waves' shuffle tree, the wave sums in order.  One segment per
+// channel in the whole launch (gridDim.y == 1): the level goes straight to power; else to part[c][segment].
+template <bool FAST>
+__global__ __launch_bounds__(kThreads) void k_channel_levels(const float2* __restrict__ X, int64_t N,
+                                                             const int32_t* __restrict__ base,
+                                                             const int64_t* __restrict__ roll,
+                                                             const int32_t* __restrict__ bw, float two_pi_over_n,
+                                                             float delta, double inv_n2, double* __restrict__ part,
+                                                             float* __restrict__ power) {
+    __shared__ double red[kThreads / 64];
+    const int c = blockIdx.x, seg = blockIdx.y, tid = threadIdx.x;
+    const int B = bw[c];
+    const int segs = min(kLevelMaxSegs, (B + kLevelSegBins - 1) / kLevelSegBins);
+    if (seg >= segs) return;   // (a narrower channel of a mixed range: workgroup-uniform)
+    const bool merge = (B & 1) == 0 && B > 2 && (int64_t)B < N;
+    const int dlo = -((B - 1) / 2);
+    const int len = merge ? B - 1 : B;   // the run: d = dlo .. dlo + len - 1
+    double acc = 0.0;
+    if (FAST) {
+        const float2* run = X + ((int64_t)base[c] + dlo);
+        const int head = (int)(((uintptr_t)run >> 3) & 1);   // 1: the first bin is the upper half of a 16-byte slot
+        const int pairs = (len - head) / 2;
+        const int per = (pairs + segs - 1) / segs;
+        const int q1 = min(pairs, (seg + 1) * per);
+        const float4* run4 = reinterpret_cast<const float4*>(run + head);
+        for (int q = seg * per + tid; q < q1; q += kThreads) {
+            const float4 v = run4[q];
+            const int d = dlo + head + 2 * q;
+            acc += level_term(v.x, v.y, level_window<true>(d, two_pi_over_n, delta)) +
+                   level_term(v.z, v.w, level_window<true>(d + 1, two_pi_over_n, delta));
+        }
+        if (seg == 0 && tid == 0) {
+            if (head && len > 0) acc += level_term(run[0].x, run[0].y, level_window<true>(dlo, two_pi_over_n, delta));
+            if ((len - head) & 1) {
+                const float2 v = run[len - 1];
+                acc += level_term(v.x, v.y, level_window<true>(dlo + len - 1, two_pi_over_n, delta));
+            }
+            if (merge) {   // Y[+B/2] = X[+B/2] w(+B/2) + X[-B/2] w(-B/2)
+                const float2 p = run[len], m = run[-1];   // d = +B/2 and d = dlo - 1 = -B/2
+                const float wp = level_window<true>(B / 2, two_pi_over_n, delta);
+                const float wm = level_window<true>(-(B / 2), two_pi_over_n, delta);
+                const float re = p.x * wp + m.x * wm, im = p.y * wp + m.y * wm;
+                acc += (double)re * re + (double)im * im;
+            }
+        }
+    } else {
+        const int64_t r = roll[c];
+        auto bin = [&](int d) {   // (d - r) mod N, |d| <= N / 2, r in [0, N)
+            int64_t i = ((int64_t)d - r) % N;
+            return X[i < 0 ? i + N : i];
+        };
+        const int per = (len + segs - 1) / segs;
+        const int e1 = min(len, (seg + 1) * per);
+        for (int e = seg * per + tid; e < e1; e += kThreads) {
+            const float2 v = bin(dlo + e);
+            acc += level_term(v.x, v.y, level_window<false>(dlo + e, two_pi_over_n, delta));
+        }
+        if (seg == 0 && tid == 0 && merge) {
+            const float2 p = bin(B / 2), m = bin(-(B / 2));
+            const float wp = level_window<false>(B / 2, two_pi_over_n, delta);
+            const float wm = level_window<false>(-(B / 2), two_pi_over_n, delta);
+            const float re = p.x * wp + m.x * wm, im = p.y * wp + m.y * wm;
+            acc += (double)re * re + (double)im * im;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid != 0) return;
+    double tot = 0.0;
+    for (int w = 0; w < kThreads / 64; ++w) tot += red[w];
+    if (gridDim.y == 1) power[c] = (float)(tot * inv_n2);
+    else part[(int64_t)c * gridDim.y + seg] = tot;
+}
+
+// The finishing launch of a split k_channel_levels: one thread per channel adds its segments' sums in segment order.
+__global__ __launch_bounds__(kThreads) void k_channel_levels_finish(const double* __restrict__ part,
+                                                                    const int32_t* __restrict__ bw, int count,
+                                                                    int max_segments, double inv_n2,
+                                                                    float* __restrict__ power) {
+    const int c = blockIdx.x * kThreads + threadIdx.x;
+    if (c >= count) return;
+    const int B = bw[c];
+    const int segs = min(kLevelMaxSegs, (B + kLevelSegBins - 1) / kLevelSegBins);
+    double tot = 0.0;
+    for (int s = 0; s < segs; ++s) tot += part[(int64_t)c * max_segments + s];
+    power[c] = (float)(tot * inv_n2);
+}
+
+constexpr int kSquelchSeg = 16 * kThreads;   // floats of a row per workgroup: four 16-byte stores per lane
+
+// Squelch on channel blockIdx.x: open = power >= threshold (false for NaN), written as one byte by the row's first
+// segment; the row of a closed channel is zero-filled, segments blockIdx.y, blockIdx.y + gridDim.y, ... of kSquelchSeg
+// floats each.  VEC (row % 4 == 0 and audio 16-byte aligned: every row is): 16-byte stores; else 4-byte ones.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_squelch(const float* __restrict__ power, const float* __restrict__ threshold,
+                                                      size_t row, float* __restrict__ audio, uint8_t* __restrict__ open) {
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const bool is_open = power[c] >= threshold[c];
+    if (open != nullptr && blockIdx.y == 0 && tid == 0) open[c] = is_open ? 1 : 0;
+    if (is_open || audio == nullptr) return;
+    float* a = audio + (size_t)c * row;
+    for (size_t s0 = (size_t)blockIdx.y * kSquelchSeg; s0 < row; s0 += (size_t)gridDim.y * kSquelchSeg) {
+        if (VEC) {
+            for (int j = 0; j < 4; ++j) {
+                const size_t i = s0 + 4 * (size_t)(j * kThreads + tid);
+                if (i < row) *reinterpret_cast<float4*>(a + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        } else {
+            for (int j = 0; j < 16; ++j) {
+                const size_t i = s0 + (size_t)(j * kThreads + tid);
+                if (i < row) a[i] = 0.f;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1209,6 +1359,43 @@ void launch_ssb_tail(float* y, int64_t n, int batch, float level, hipStream_t st
         hipLaunchKernelGGL(k_ssb_tail<true>, dim3((unsigned)batch), dim3(kThreads), 0, stream, y, n, level);
     else
         hipLaunchKernelGGL(k_ssb_tail<false>, dim3((unsigned)batch), dim3(kThreads), 0, stream, y, n, level);
+    RC_LAUNCH_CHECK();
+}
+
+int level_segments(int64_t B) { return (int)std::min<int64_t>(kLevelMaxSegs, (B + kLevelSegBins - 1) / kLevelSegBins); }
+
+void launch_channel_levels(const float2* X, int64_t N, const int32_t* base, const int64_t* roll, const int32_t* bw,
+                           int count, int max_segments, double* part, float* power, hipStream_t stream) {
+    if (count <= 0) return;
+    RC_REQUIRE(max_segments >= 1 && max_segments <= kLevelMaxSegs && (max_segments == 1 || part != nullptr), RCFM_ERR_RUNTIME,
+               "bad segment count of the level sums");
+    const float two_pi_over_n = (float)(6.28318530717958647692 / (double)N);
+    const float delta = (N % 2) ? (float)(3.14159265358979323846 / (double)N) : 0.f;
+    const double inv_n2 = 1.0 / ((double)N * (double)N);
+    const dim3 grid((unsigned)count, (unsigned)max_segments, 1);
+    if (base != nullptr)
+        hipLaunchKernelGGL(k_channel_levels<true>, grid, dim3(kThreads), 0, stream, X, N, base, roll, bw, two_pi_over_n, delta,
+                           inv_n2, part, power);
+    else
+        hipLaunchKernelGGL(k_channel_levels<false>, grid, dim3(kThreads), 0, stream, X, N, base, roll, bw, two_pi_over_n, delta,
+                           inv_n2, part, power);
+    RC_LAUNCH_CHECK();
+    if (max_segments > 1) {
+        hipLaunchKernelGGL(k_channel_levels_finish, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
+                           part, bw, count, max_segments, inv_n2, power);
+        RC_LAUNCH_CHECK();
+    }
+}
+
+void launch_squelch(const float* power, const float* threshold, int count, size_t row, float* audio, uint8_t* open,
+                    hipStream_t stream) {
+    if (count <= 0 || (audio == nullptr && open == nullptr)) return;
+    const size_t segs = audio != nullptr ? (row + kSquelchSeg - 1) / kSquelchSeg : 1;
+    const dim3 grid((unsigned)count, (unsigned)std::min<size_t>(std::max<size_t>(segs, 1), 65535), 1);
+    if (row % 4 == 0 && (uintptr_t)audio % 16 == 0)
+        hipLaunchKernelGGL(k_squelch<true>, grid, dim3(kThreads), 0, stream, power, threshold, row, audio, open);
+    else
+        hipLaunchKernelGGL(k_squelch<false>, grid, dim3(kThreads), 0, stream, power, threshold, row, audio, open);
     RC_LAUNCH_CHECK();
 }
 

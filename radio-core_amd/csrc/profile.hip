@@ -9,7 +9,8 @@ const char* const kStageNames[ST_COUNT] = {
     "tuner_fft_N",   "tuner_gather",  "tuner_ifft_B", "discriminator", "pilot_stage",
     "rfft_B",        "hilbert_mask",  "ifft_B",       "stereo_mix",    "fft_B",
     "audio_spectrum", "ifft_A",       "deemphasis",   "deemph_state",  "dc_clip",
-    "lds_chain",     "envelope",      "am_tail",      "ssb_tail"};
+    "lds_chain",     "envelope",      "am_tail",      "ssb_tail",
+    "levels",        "squelch"};
 }  // namespace
 
 Profiler g_prof;

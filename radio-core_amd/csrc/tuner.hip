@@ -126,6 +126,13 @@ bool rcfm_tuner_s::fast_gather_ok(int first) {
     return series && halo >= B / 2 + 1 && g.nyq_mode != NYQ_UP && B <= n;
 }
 
+// The same preconditions for reading a channel of bandwidth B as one run of the haloed spectrum (levels()); no band is
+// built for it.  (B <= n always holds here, so the Nyquist rule is never the up-sampling one.)
+bool rcfm_tuner_s::fast_bins_ok(int32_t B) const {
+    const bool series = 6.28318530717958647692 * ((double)(B / 2 + 2) / (double)n) < 0.25;
+    return halo > 0 && series && halo >= B / 2 + 1 && B <= n;
+}
+
 // Can run() leave angle(x) / pi instead of x for this channel's band?  (engine path only)
 bool rcfm_tuner_s::phase_capable(int first) { return first >= 0 && first < nch && band(bw[first]).engine != nullptr; }
 
@@ -137,15 +144,40 @@ int rcfm_tuner_s::band_row_length(int first) { return phase_capable(first) ? (in
 bool rcfm_tuner_s::band_two_pass(int first) { return phase_capable(first) && band(bw[first]).engine->npass() == 2; }
 
 // Channels [first, first + count) may be read from the loaded spectrum: it was loaded, for a shard and into a storage
-// that hold them, and they share one bandwidth (else bw_code / bw_msg).  `caller` names the entry point in the error.
-void rcfm_tuner_s::require_readable(int first, int count, const char* caller, int bw_code, const char* bw_msg) const {
+// that hold them.  `caller` names the entry point in the error.
+void rcfm_tuner_s::require_loaded(int first, int count, const char* caller) const {
     RC_REQUIRE(loaded, RCFM_ERR_STATE, std::string(caller) + " called before rcfm_tuner_load");
     RC_REQUIRE(!loaded_windowed || (first >= loaded_first && first + count <= loaded_first + loaded_count),
                RCFM_ERR_STATE,
                "channel outside the shard the spectrum was loaded for (rcfm_tuner_shard, then rcfm_tuner_load)");
     RC_REQUIRE(!ext_window || (first >= ext_first && first + count <= ext_first + ext_count), RCFM_ERR_STATE,
                "channel outside the window the attached storage holds (rcfm_tuner_attach_window)");
+}
+
+// ... and they share one bandwidth (else bw_code / bw_msg).
+void rcfm_tuner_s::require_readable(int first, int count, const char* caller, int bw_code, const char* bw_msg) const {
+    require_loaded(first, count, caller);
     for (int i = 0; i < count; ++i) RC_REQUIRE(bw[first + i] == bw[first], bw_code, bw_msg);
+}
+
+// power[i] = the level of channel first + i (include/rcfm.h, rcfm_tuner_levels): one read of the channel's bins.  The
+// fast form needs every channel of the range to pass fast_bins_ok; the number of workgroups a channel is split over
+// depends on its bandwidth alone (level_segments), so the sums have one order on every device and stream.
+void rcfm_tuner_s::levels(int first, int count, float* power, hipStream_t s) {
+    require_channels(first, count, nch);
+    require_loaded(first, count, "rcfm_tuner_levels");
+    if (count == 0) return;
+    bool fast = true;
+    int segs = 1;
+    for (int c = first; c < first + count; ++c) {
+        RC_REQUIRE(bw[c] <= n, RCFM_ERR_ARG, "channel bandwidth exceeds the input bandwidth");
+        fast = fast && fast_bins_ok(bw[c]);
+        segs = std::max(segs, level_segments(bw[c]));
+    }
+    if (segs > 1) levels_part.reserve(sizeof(double) * (size_t)count * segs);
+    StageTimer tm(ST_LEVELS, s);
+    launch_channel_levels(spectrum(), n, fast ? base_dev.as<int32_t>() + first : nullptr, roll_dev.as<int64_t>() + first,
+                          bw_dev.as<int32_t>() + first, count, segs, segs > 1 ? levels_part.as<double>() : nullptr, power, s);
 }
 
 // theta != nullptr (phase_capable bands only): angle(x) / pi goes to theta [count][B] float32, out is unused;
@@ -209,6 +241,7 @@ int rcfm_tuner_create(int64_t n, int nch, const int64_t* roll_host, const int32_
             t->roll[i] = r;
         }
         if (nch) t->roll_dev.upload(t->roll.data(), sizeof(int64_t) * nch);
+        if (nch) t->bw_dev.upload(t->bw.data(), sizeof(int32_t) * nch);
         // halo: whole 128-byte lines on both sides, wide enough for the widest channel
         int64_t h = 0;
         for (int i = 0; i < nch; ++i) h = std::max<int64_t>(h, bw_host[i] / 2 + 2);
@@ -287,6 +320,25 @@ int rcfm_tuner_run(rcfm_tuner_t t, int first, int count, void* out, void* stream
         RC_REQUIRE(t && out, RCFM_ERR_ARG, "NULL argument");
         ArenaScope scope(t->arena);
         t->run(first, count, static_cast<float2*>(out), as_stream(stream));
+    });
+}
+
+int rcfm_tuner_levels(rcfm_tuner_t t, int first, int count, void* power, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(t && power, RCFM_ERR_ARG, "NULL argument");
+        ArenaScope scope(t->arena);
+        t->levels(first, count, static_cast<float*>(power), as_stream(stream));
+    });
+}
+
+int rcfm_squelch(const void* power, const void* threshold, int count, size_t floats_per_channel, void* audio, void* open,
+                 void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(power && threshold, RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(count >= 0, RCFM_ERR_ARG, "negative channel count");
+        StageTimer tm(ST_SQUELCH, as_stream(stream));
+        launch_squelch(static_cast<const float*>(power), static_cast<const float*>(threshold), count, floats_per_channel,
+                       static_cast<float*>(audio), static_cast<uint8_t*>(open), as_stream(stream));
     });
 }
 

@@ -43,7 +43,8 @@ class Lanes:
         self._tuners = [tuner] + [tuner._lane_clone() for _ in range(depth - 1)]
         self._streams = [self._torch.cuda.Stream() for _ in range(depth)]
         self._next = 0
-        self._pending = {}          # ticket -> (end event, audio tensor, event behind the load = last reader of the input)
+        self._pending = {}          # ticket -> (end event, audio tensor, event behind the load = last reader of the input,
+                                    #            the squelch's device masks or None)
         self._spans = {}            # timing=True: ticket -> (start event, end event)
 
     @property
@@ -53,7 +54,8 @@ class Lanes:
     def submit(self, input_signal, chunk: int = 0, each: bool = False) -> int:
         """Queue Tuner.load + Tuner.run_all of one buffer on the next lane; returns a ticket for ``result``.
         each=True: Tuner.run_each instead (channels of different classes and geometries; ``result`` then returns its
-        list of per-channel arrays)."""
+        list of per-channel arrays).  With ``tuner.set_squelch`` set, the lane queues the levels and the squelch behind
+        its demodulators like ``run_all`` does; ``result(ticket, open_mask=True)`` returns the buffer's mask."""
         ticket = self._next
         self._next += 1
         k = ticket % len(self._tuners)
@@ -72,7 +74,7 @@ class Lanes:
             loaded = self._event(st)            # the wideband FFT is the LAST reader of the input buffer
             audio = t._run_each_device() if each else t._run_all_device(chunk)
             ev = self._event(st)
-        self._pending[ticket] = (ev, audio, loaded)
+        self._pending[ticket] = (ev, audio, loaded, t._open)
         if self._timing:
             self._spans[ticket] = (start, ev)
         return ticket
@@ -90,9 +92,11 @@ class Lanes:
         _, end = self._spans[earlier]
         return float(start.elapsed_time(end))
 
-    def result(self, ticket: int, numpy_output: bool = True):
-        """The audio of one submitted buffer, [C, A, ch] float32 (the shard's block after Tuner.shard)."""
-        ev, audio, _ = self._pending.pop(ticket)
+    def result(self, ticket: int, numpy_output: bool = True, open_mask: bool = False):
+        """The audio of one submitted buffer, [C, A, ch] float32 (the shard's block after Tuner.shard).
+        open_mask=True: ``(audio, mask)`` with the squelch's numpy bool [C] of that buffer (Tuner.open_mask; None when
+        the buffer was submitted with squelch off)."""
+        ev, audio, _, masks = self._pending.pop(ticket)
         device_output = self._base._cuda and not numpy_output
         if device_output:
             cur = self._torch.cuda.current_stream()
@@ -102,8 +106,12 @@ class Lanes:
         else:
             ev.synchronize()
         if isinstance(audio, list):                            # submit(each=True): Tuner.run_each's list
-            return self._base._each_result(audio, device_output)
-        return audio if device_output else hip.to_host(audio)
+            out = self._base._each_result(audio, device_output)
+        else:
+            out = audio if device_output else hip.to_host(audio)
+        if not open_mask:
+            return out
+        return out, (Tuner._mask_result(masks) if masks is not None else None)
 
     def hold_current_stream(self, ticket: int):
         """Order the CURRENT stream behind the last READ of one submitted buffer's input (the wideband FFT of
@@ -122,5 +130,5 @@ class Lanes:
 
     def drain(self):
         """Wait for everything submitted so far (results stay collectable)."""
-        for ev, _, _ in self._pending.values():
-            ev.synchronize()
+        for entry in self._pending.values():
+            entry[0].synchronize()

@@ -67,6 +67,9 @@ class Tuner(Injector):
         self._state_owner = {}     # (kind, C, B, A, tau) -> the batched handle whose buffer holds that geometry's state
         self._bound_version = {}   # batched key -> channel-list version its demodulators were bound at
         self._state_fence = False  # Lanes: this tuner's batched handles run on several streams (RCFM_OPT_STATE_FENCE)
+        self._squelch = None       # set_squelch: None (off) or float32 thresholds, 0-d (every channel) or [len(channels())]
+        self._squelch_dev = None   # (channel-list version, device float32 [C]): rebuilt when either changes
+        self._open = None          # device uint8 masks of the last run_all / run_each, one per launch group
 
     @property
     def input_frequency(self) -> float:
@@ -279,6 +282,67 @@ class Tuner(Injector):
         hip.check(self._lib.rcfm_tuner_run(handle, first, count, hip.ptr(out), hip.stream()))
         return out
 
+    # ---- signal levels and squelch (rcfm_tuner_levels / rcfm_squelch; no reference counterpart) ----------------------
+
+    def levels(self, numpy_output: bool = True):
+        """Signal level of every channel (of the shard's range after ``shard``), float32 [count]: the mean power
+        ``mean(|run(i)|**2)`` of the channel's samples, linear, in the units of the input samples -- read from the
+        loaded spectrum without the inverse FFT.  Valid after ``load`` / ``adopt``; the channels may differ in bandwidth."""
+        handle = self._ready()
+        _, first, count = self._launch_plan()
+        power = hip.empty((count,), self._torch.float32)
+        hip.check(self._lib.rcfm_tuner_levels(handle, first, count, hip.ptr(power), hip.stream()))
+        return self._result(power, self._cuda and not numpy_output)
+
+    def set_squelch(self, threshold=None):
+        """Mute what is below a level: from now on ``run_all`` / ``run_each`` (and ``Lanes.submit``) compare every
+        channel's level of the buffer with its threshold -- a scalar, or a sequence of ``len(channels())``, in the units
+        of ``levels()`` -- and return exact zeros for the channels below it; ``open_mask()`` tells which were open.  The
+        decision is per buffer, on the device and on the caller's stream (no host synchronisation), and the
+        demodulators still run on every channel: the de-emphasis state advances as without squelch.  A NaN threshold
+        keeps a channel closed.  ``None`` (the default) turns squelch off: nothing more is launched than before.
+        ``squelch.threshold_over_floor`` derives thresholds from a ``levels()`` pass."""
+        if threshold is None:
+            self._squelch = None
+        else:
+            a = np.array(threshold, dtype=np.float32)      # (a copy: a new object per setting, lanes compare by identity)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != len(self._bounds)):
+                raise ValueError("squelch thresholds: a scalar or one per channel (%d)" % len(self._bounds))
+            self._squelch = a
+        self._squelch_dev = None
+        self._open = None
+
+    def open_mask(self):
+        """numpy bool [count]: which channels the squelch left open in this tuner's last ``run_all`` / ``run_each``."""
+        if self._open is None:
+            raise RuntimeError("open_mask: no run_all / run_each with squelch set (set_squelch) yet")
+        return self._mask_result(self._open)
+
+    @staticmethod
+    def _mask_result(masks):
+        return np.concatenate([hip.to_host(m) for m in masks]).astype(bool) if masks else np.zeros(0, bool)
+
+    def _thresholds(self):
+        if self._squelch_dev is None or self._squelch_dev[0] != self._version:
+            a = self._squelch
+            if a.ndim == 1 and a.shape[0] != len(self._bounds):
+                raise ValueError("squelch thresholds were set for %d channels, the tuner has %d"
+                                 % (a.shape[0], len(self._bounds)))
+            full = np.ascontiguousarray(np.broadcast_to(a, (len(self._bounds),)))
+            self._squelch_dev = (self._version, hip.to_device(full, self._torch.float32))
+        return self._squelch_dev[1]
+
+    def _squelch_group(self, handle, first, count, audio):
+        # behind the group's rcfm_pipeline_run on the same stream: levels of its channels, then mask + zero fill
+        thr = self._thresholds()
+        power = hip.empty((count,), self._torch.float32)
+        mask = hip.empty((count,), self._torch.uint8)
+        s = hip.stream()
+        hip.check(self._lib.rcfm_tuner_levels(handle, first, count, hip.ptr(power), s))
+        hip.check(self._lib.rcfm_squelch(hip.ptr(power), ctypes.c_void_p(thr.data_ptr() + 4 * first), count,
+                                         audio.numel() // count, hip.ptr(audio), hip.ptr(mask), s))
+        return mask
+
     def _launch_plan(self):
         """Groups of consecutive channels that share demodulator class, geometry and bandwidth, for the declared
         shard: [(first, count, kind, B, A, tau)], built once per channel-list version (O(C)) -- the steady
@@ -327,6 +391,7 @@ class Tuner(Injector):
         audio = hip.empty((count, A, ch), self._torch.float32)
         hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk), first, count,
                                               hip.ptr(audio), hip.stream()))
+        self._open = [self._squelch_group(handle, first, count, audio)] if self._squelch is not None and count else None
         return audio
 
     def _plan_uniform(self):
@@ -354,6 +419,7 @@ class Tuner(Injector):
         handle = self._ready()
         groups, first, count = self._launch_plan()
         blocks = []
+        masks = [] if self._squelch is not None else None
         for i, n, kind, B, A, tau in groups:
             if kind is None:
                 raise ValueError("run_each needs an FM, MFM, WBFM, AM, USB or LSB demodulator on every channel")
@@ -361,7 +427,10 @@ class Tuner(Injector):
             audio = hip.empty((n, A, ch), self._torch.float32)
             hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, 0), i, n,
                                                   hip.ptr(audio), hip.stream()))
+            if masks is not None:
+                masks.append(self._squelch_group(handle, i, n, audio))
             blocks.append((n, ch, audio))
+        self._open = masks
         return blocks
 
     def _each_result(self, blocks, device_output):
@@ -467,6 +536,8 @@ class Tuner(Injector):
         return t
 
     def _sync_lane(self, base):
+        if self._squelch is not base._squelch:             # the base's squelch setting (a new object per set_squelch)
+            self._squelch, self._squelch_dev, self._open = base._squelch, None, None
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
                 self._input_bandwidth == base._input_bandwidth:
             return

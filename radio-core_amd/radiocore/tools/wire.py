@@ -13,12 +13,18 @@ import numpy as np
 __all__ = ["frames", "parse_frame"]
 
 
-def frames(channels, audio):
-    """[(address_bytes, payload_bytes)] for a [C, A, ch] block, in channel order."""
+def frames(channels, audio, open_mask=None):
+    """[(address_bytes, payload_bytes)] for a [C, A, ch] block, in channel order.  open_mask (bool [C], Tuner.open_mask):
+    channels the squelch closed produce no message."""
     audio = np.ascontiguousarray(audio, dtype=np.float32)
     if audio.ndim != 3 or audio.shape[0] != len(channels):
         raise ValueError("audio must be [channels, samples, audio_channels]")
-    return [[ch.address_bytes, audio[i].tobytes()] for i, ch in enumerate(channels)]
+    if open_mask is None:
+        return [[ch.address_bytes, audio[i].tobytes()] for i, ch in enumerate(channels)]
+    open_mask = np.asarray(open_mask, dtype=bool)
+    if open_mask.shape != (len(channels),):
+        raise ValueError("open_mask must hold one flag per channel")
+    return [[ch.address_bytes, audio[i].tobytes()] for i, ch in enumerate(channels) if open_mask[i]]
 
 
 def parse_frame(message, audio_channels):
