@@ -287,6 +287,14 @@ int rcfm_comm_destroy(rcfm_comm_t c);
 
 /* ---- primitives (class parity with radiocore/analog) ---------------------- */
 
+/* Limits, checked on the host before anything is launched (RCFM_ERR_ARG beyond them):
+ *   C      1 .. 65535 signals per call, for every entry point that takes C (rcfm_resampler_create, rcfm_filtfilt,
+ *          rcfm_lfilter_fir, rcfm_hilbert, rcfm_discriminator): the signal index is a grid coordinate
+ *   ntaps  rcfm_filtfilt 1 .. 2867, rcfm_lfilter_fir 1 .. 5461: the kernels keep the taps and a tile of the signal
+ *          in 64 KiB of LDS
+ *   count  rcfm_pll_phase: at most 4 294 967 040 samples (one thread each)
+ * Arrays are dense: signal c starts at element c * n (c * m for the resampler's output). */
+
 /* Decimate, decimate.py:21-50 = scipy.signal.resample with the fftshifted
  * periodic Hamming window: C signals of n samples -> m samples.
  * is_complex = 0: float32 in/out; 1: complex64 in/out (receive_fm.py:80). */
@@ -300,17 +308,22 @@ int rcfm_resampler_destroy(rcfm_resampler_t r);
 int rcfm_filtfilt(int C, int n, const float* taps_host, int ntaps, const void* x, void* y,
                   void* stream);
 /* Deemphasis.run, deemphasis.py:51-66 = lfilter(taps, 1, x, zi=state):
- * x [C][n] -> y [C][n] float32; state [C][ntaps-1] float32 DEVICE, updated in place. */
+ * x [C][n] -> y [C][n] float32; state [C][ntaps-1] float32 DEVICE, updated in place (one state per signal; may be
+ * NULL for ntaps = 1, which has none).  n may be shorter than the state: what is left of it moves up, as in lfilter.
+ * NOT in place: x [C][n] and y [C][n] must not overlap; y == x and any partial overlap are refused with RCFM_ERR_ARG
+ * (the final state is built from x after y is written, and a tile of y needs the inputs before it). */
 int rcfm_lfilter_fir(int C, int n, const float* taps_host, int ntaps, void* state, const void* x,
                      void* y, void* stream);
 /* PLL.step, pll.py:25-34 = scipy.signal.hilbert: x [C][n] float32 -> z [C][n] complex64. */
 int rcfm_hilbert(int C, int n, const void* x, void* z, void* stream);
 /* PLL.real / PLL.image, pll.py:36-58: out = Re or Im of z^mult / |z^mult|;
  * z [count] complex64 -> out [count] float32.  Integer mult in [1, 64] is multiplied
- * out like numpy's complex power; any other mult uses the principal branch. */
+ * out like numpy's complex power (and overflows / underflows to NaN like it when |z|^mult leaves float32); any other
+ * mult uses the principal branch, cos / sin(mult arg z), whatever |z|.  z = 0 gives NaN, except for mult = 0 (1, 0). */
 int rcfm_pll_phase(const void* z, size_t count, double mult, int want_imag, void* out,
                    void* stream);
-/* FM discriminator, fm.py:60-65: iq [C][n] complex64 -> d [C][n] float32 (d[0] = 0). */
+/* FM discriminator, fm.py:60-65: iq [C][n] complex64 -> d [C][n] float32; d[c][0] = 0 for every signal c (no
+ * difference is taken across signals). */
 int rcfm_discriminator(int C, int n, const void* iq, void* d, void* stream);
 
 /* ---- FFT engine (the hand-written replacement of cupy.fft / scipy.fft calls) -- */

@@ -91,6 +91,15 @@ void launch_stereo_mix(const float2* z, const float* m, float2* u, size_t count,
 void launch_pll_phase(const float2* z, size_t count, double mult, int want_imag, float* out,
                       hipStream_t stream);
 
+// Launch limits of the generic (any tap count, any batch) kernels; the entry points of rcfm.h check them on the host
+// before anything is launched.  The batch index is a grid y / z coordinate (at most 65535).  The dynamic LDS of k_fir
+// (2 nb + 1031 floats), k_fir_state (3 nb floats) and k_pilot_stage (5 H + 2051 floats, H = ntaps - 1) grows with the
+// tap count and has to fit the 64 KiB a launch gets without asking for more: nb <= 5461 (k_fir_state binds; k_fir
+// alone would take 7676) and H <= 2866.  kernels.hip asserts both against the tile sizes.
+constexpr int kMaxBatch = 65535;
+constexpr int kFirMaxTaps = 5461;
+constexpr int kPilotMaxTaps = 2867;
+
 // lfilter(taps, 1, x, zi=state) for an FIR (deemphasis.py:64).  x, y: [batch][n][ch]
 // interleaved; state: [batch][ch][nb-1] transposed-direct-form-II state (read only).
 // partial (optional): [batch][ch][fir_tiles(n)] per-tile sums of y for the DC removal.

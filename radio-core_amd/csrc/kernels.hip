@@ -558,7 +558,8 @@ __global__ __launch_bounds__(kThreads) void k_pll_phase(const float2* __restrict
         out[i] = (want_imag ? w.y : w.x) / mag;
     } else {
         const double th = mult * atan2((double)v.y, (double)v.x);
-        const bool zero = (v.x == 0.f && v.y == 0.f);
+        // 0^mult / |0^mult| is 0 / 0 -- but for mult = 0, where numpy's power is 1 whatever the base
+        const bool zero = (v.x == 0.f && v.y == 0.f) && mult != 0.0;
         const double r = want_imag ? sin(th) : cos(th);
         out[i] = zero ? __builtin_nanf("") : (float)r;
     }
@@ -1240,10 +1241,23 @@ void launch_pilot_stage_h40_phase(const float* theta, float* m_out, float* p_out
     launch_pilot_stage_h40_t(theta, m_out, p_out, n, batch, g_host, side_tap, stream, blk);
 }
 
+// Dynamic LDS of the generic FIR kernels, and the tap counts kernels.h promises to fit into kLdsNoOptIn.
+constexpr size_t kLdsNoOptIn = 64 * 1024;
+constexpr size_t pilot_lds_bytes(int H) {
+    return sizeof(float) * ((size_t)(H + 1) + (kPilotTile + 2 * H) + (kPilotTile + 2 * H + 2));
+}
+constexpr size_t fir_lds_bytes(int nb) { return sizeof(float) * ((size_t)nb + (kFirTile + nb - 1) + 8); }
+constexpr size_t fir_state_lds_bytes(int nb) { return sizeof(float) * (3 * (size_t)nb); }
+static_assert(pilot_lds_bytes(kPilotMaxTaps - 1) <= kLdsNoOptIn && pilot_lds_bytes(kPilotMaxTaps) > kLdsNoOptIn,
+              "kPilotMaxTaps (kernels.h, rcfm.h) is not the largest tap count k_pilot_stage can launch");
+static_assert(fir_lds_bytes(kFirMaxTaps) <= kLdsNoOptIn && fir_state_lds_bytes(kFirMaxTaps) <= kLdsNoOptIn &&
+                  fir_state_lds_bytes(kFirMaxTaps + 1) > kLdsNoOptIn,
+              "kFirMaxTaps (kernels.h, rcfm.h) is not the largest tap count k_fir + k_fir_state can launch");
+
 void launch_pilot_stage(const float2* iq, const float* x, float* m_out, float* p_out, int64_t n,
                         int batch, const float* g, int H, float side_tap, hipStream_t stream) {
     if (batch <= 0) return;
-    const size_t lds = sizeof(float) * ((size_t)(H + 1) + (kPilotTile + 2 * H) + (kPilotTile + 2 * H + 2));
+    const size_t lds = pilot_lds_bytes(H);
     hipLaunchKernelGGL(k_pilot_stage, grid2(n, kPilotTile, batch), dim3(kThreads), lds, stream, iq, x, m_out,
                        p_out, n, g, H, side_tap);
     RC_LAUNCH_CHECK();
@@ -1271,7 +1285,7 @@ int fir_tiles(int64_t n) { return (int)((n + kFirTile - 1) / kFirTile); }
 void launch_fir(const float* x, float* y, int64_t n, int ch, int batch, const float* taps, int nb,
                 const float* state, float* partial, hipStream_t stream) {
     if (batch <= 0 || n <= 0) return;
-    const size_t lds = sizeof(float) * ((size_t)nb + (kFirTile + nb - 1) + 8);
+    const size_t lds = fir_lds_bytes(nb);
     hipLaunchKernelGGL(k_fir, dim3((unsigned)fir_tiles(n), (unsigned)ch, (unsigned)batch), dim3(kThreads), lds,
                        stream, x, y, n, ch, taps, nb, state, partial);
     RC_LAUNCH_CHECK();
@@ -1311,7 +1325,7 @@ void launch_fir51(const float* x, float* y, int64_t n, int ch, int batch, const 
 void launch_fir_state(const float* x, int64_t n, int ch, int batch, const float* taps, int nb,
                       float* state, hipStream_t stream, int row_samples, int row_pitch_samples) {
     if (batch <= 0 || nb < 2) return;
-    hipLaunchKernelGGL(k_fir_state, dim3((unsigned)(batch * ch)), dim3(128), sizeof(float) * (3 * nb), stream,
+    hipLaunchKernelGGL(k_fir_state, dim3((unsigned)(batch * ch)), dim3(128), fir_state_lds_bytes(nb), stream,
                        x, n, ch, taps, nb, state, row_layout(n, ch, row_samples, row_pitch_samples));
     RC_LAUNCH_CHECK();
 }

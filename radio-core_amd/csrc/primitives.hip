@@ -100,6 +100,10 @@ HilbertPlan& hilbert_plan(int n, int C, hipStream_t s) {
     return *it->second;
 }
 std::mutex g_hilbert_mu;
+
+// every batched entry point carries the signal index in a grid y / z coordinate (kernels.h)
+const char* const kBatchLimit = "at most 65535 signals per call";
+static_assert(kMaxBatch == 65535, "kBatchLimit and rcfm.h state the batch limit in words");
 }  // namespace
 
 extern "C" {
@@ -110,6 +114,7 @@ int rcfm_resampler_create(int C, int n, int m, int is_complex, rcfm_resampler_t*
     return guarded([&] {
         RC_REQUIRE(out != nullptr, RCFM_ERR_ARG, "out is NULL");
         RC_REQUIRE(C >= 1 && n >= 1 && m >= 1, RCFM_ERR_ARG, "bad resampler size");
+        RC_REQUIRE(C <= kMaxBatch, RCFM_ERR_ARG, kBatchLimit);
         auto r = std::make_unique<rcfm_resampler_s>();
         r->C = C;
         r->n = n;
@@ -186,6 +191,9 @@ int rcfm_filtfilt(int C, int n, const float* taps_host, int ntaps, const void* x
     return guarded([&] {
         RC_REQUIRE(taps_host && x && y, RCFM_ERR_ARG, "NULL argument");
         RC_REQUIRE(C >= 1 && ntaps >= 1, RCFM_ERR_ARG, "bad filtfilt size");
+        RC_REQUIRE(C <= kMaxBatch, RCFM_ERR_ARG, kBatchLimit);
+        RC_REQUIRE(ntaps <= kPilotMaxTaps, RCFM_ERR_ARG,
+                   "rcfm_filtfilt takes at most " + std::to_string(kPilotMaxTaps) + " taps");
         RC_REQUIRE(n > 3 * ntaps, RCFM_ERR_ARG,
                    "The length of the input vector x must be greater than padlen, which is " +
                        std::to_string(3 * ntaps) + ".");
@@ -201,6 +209,18 @@ int rcfm_lfilter_fir(int C, int n, const float* taps_host, int ntaps, void* stat
     return guarded([&] {
         RC_REQUIRE(taps_host && x && y && (state || ntaps < 2), RCFM_ERR_ARG, "NULL argument");
         RC_REQUIRE(C >= 1 && n >= 1 && ntaps >= 1, RCFM_ERR_ARG, "bad lfilter size");
+        RC_REQUIRE(C <= kMaxBatch, RCFM_ERR_ARG, kBatchLimit);
+        RC_REQUIRE(ntaps <= kFirMaxTaps, RCFM_ERR_ARG,
+                   "rcfm_lfilter_fir takes at most " + std::to_string(kFirMaxTaps) + " taps");
+        // k_fir's workgroups read the previous tile's tail of x while others write y, and k_fir_state reads x after y is
+        // complete: in place, both would see outputs where they need inputs
+        {
+            const char* xb = static_cast<const char*>(x);
+            const char* yb = static_cast<const char*>(y);
+            const size_t bytes = (size_t)C * (size_t)n * sizeof(float);
+            RC_REQUIRE(xb + bytes <= yb || yb + bytes <= xb, RCFM_ERR_ARG,
+                       "rcfm_lfilter_fir does not run in place: x and y must not overlap");
+        }
         hipStream_t s = as_stream(stream);
         const std::shared_ptr<DeviceBuffer> td = cached_taps(std::vector<float>(taps_host, taps_host + ntaps));
         launch_fir(static_cast<const float*>(x), static_cast<float*>(y), n, 1, C, td->as<float>(), ntaps,
@@ -213,6 +233,7 @@ int rcfm_hilbert(int C, int n, const void* x, void* z, void* stream) {
     return guarded([&] {
         RC_REQUIRE(x && z, RCFM_ERR_ARG, "NULL argument");
         RC_REQUIRE(C >= 1 && n >= 1, RCFM_ERR_ARG, "bad hilbert size");
+        RC_REQUIRE(C <= kMaxBatch, RCFM_ERR_ARG, kBatchLimit);
         hipStream_t s = as_stream(stream);
         std::lock_guard<std::mutex> lock(g_hilbert_mu);   // the cache itself; the kernels are ordered by their stream
         HilbertPlan& p = hilbert_plan(n, C, s);
@@ -231,6 +252,8 @@ int rcfm_hilbert(int C, int n, const void* x, void* z, void* stream) {
 int rcfm_pll_phase(const void* z, size_t count, double mult, int want_imag, void* out, void* stream) {
     return guarded([&] {
         RC_REQUIRE(z && out, RCFM_ERR_ARG, "NULL argument");
+        // one thread per sample, and a grid holds fewer than 2^32 threads
+        RC_REQUIRE(count <= (size_t)4294967040u, RCFM_ERR_ARG, "at most 4294967040 samples per call");
         launch_pll_phase(static_cast<const float2*>(z), count, mult, want_imag, static_cast<float*>(out),
                          as_stream(stream));
     });
@@ -239,6 +262,8 @@ int rcfm_pll_phase(const void* z, size_t count, double mult, int want_imag, void
 int rcfm_discriminator(int C, int n, const void* iq, void* d, void* stream) {
     return guarded([&] {
         RC_REQUIRE(iq && d, RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(C >= 1 && n >= 1, RCFM_ERR_ARG, "bad discriminator size");
+        RC_REQUIRE(C <= kMaxBatch, RCFM_ERR_ARG, kBatchLimit);
         launch_discriminator(static_cast<const float2*>(iq), static_cast<float*>(d), n, C, as_stream(stream));
     });
 }
