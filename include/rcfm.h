@@ -42,7 +42,8 @@ extern "C" {
 
 #define RCFM_VERSION 102 /* 0.1.2: tooling entry points moved to rcfm_tools.h (same symbols), RCFM_OPT_GRAPH;
                             demodulator kinds RCFM_AM, RCFM_USB, RCFM_LSB (no new entry points);
-                            rcfm_tuner_levels and rcfm_squelch added (new symbols only, nothing existing changed) */
+                            rcfm_tuner_levels and rcfm_squelch added (new symbols only, nothing existing changed);
+                            rcfm_tuner_power_spectrum added (a new symbol only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -169,6 +170,27 @@ int rcfm_tuner_levels(rcfm_tuner_t t, int first, int count, void* power, void* s
  * squelch and a channel that reopens carries the audio it would have carried anyway. */
 int rcfm_squelch(const void* power, const void* threshold, int count, size_t floats_per_channel,
                  void* audio, void* open, void* stream);
+/* ---- wideband power spectrum (no reference counterpart) ------------------------------------------------------------
+ * What the band looks like between and around the channels: binned power and peak of the loaded spectrum X (unnormalised,
+ * n bins).  A signed bin s in [-floor(n/2), n - floor(n/2)) means X[s mod n]; ascending s is ascending frequency, the
+ * order numpy.fft.fftshift gives, and with one-second buffers s is Hz from the input frequency.  A span [s0, s0 + L),
+ * L >= 1, lies inside that interval (it never wraps in frequency) and is cut into M cells, 1 <= M <= L: cell m covers
+ * span positions e in [floor(m L / M), floor((m + 1) L / M)) (products in 64-bit integers), so cells differ in length
+ * by at most one bin and none is empty.
+ *   power[m] = sum over the cell of |X[(s0 + e) mod n]|^2 / n^2      float32
+ *   peak[m]  = max over the cell of |X[(s0 + e) mod n]|^2 / n^2      float32
+ * Linear power in the units of the input samples, the unit of rcfm_tuner_levels; over the full span the cells' power
+ * adds up to mean(|x|^2) (Parseval).  peak keeps a narrow carrier visible in a wide cell.  Each |X|^2 is formed in float64
+ * from the float32 re and im, summed in float64, scaled by 1 / n^2 in float64 and rounded to float32 once.
+ * RCFM_ERR_ARG (checked before any device call): NULL handle, both outputs NULL, L < 1, M < 1, M > L, a span outside the
+ * signed interval.  RCFM_ERR_STATE: before a load, or when a bin of the span is not held -- after a plain load (also into
+ * an attached spectrum) every bin is; after a sharded load, an adopt or with a window attached, the bins of
+ * rcfm_tuner_window for the range in force, containment taken modulo n.
+ * The order of every sum depends on (n, s0, L, M) alone and there are no floating-point atomics: bit-identical from run
+ * to run, from stream to stream, and whether one output is NULL or both are present.
+ * first_bin = s0, nbins = L, cells = M; power, peak: [M] float32 device, either may be NULL */
+int rcfm_tuner_power_spectrum(rcfm_tuner_t t, int64_t first_bin, int64_t nbins, int64_t cells, void* power, void* peak,
+                              void* stream);
 int rcfm_tuner_destroy(rcfm_tuner_t t);
 
 /* ---- demodulators (radiocore/analog/{fm,mfm,wbfm}.py) --------------------- */

@@ -202,6 +202,7 @@ struct rcfm_tuner_s {
     rcfm::DeviceBuffer base_dev;   // int32 (n - roll) mod n per channel: start of the channel in the haloed spectrum
     rcfm::DeviceBuffer bw_dev;     // int32 bandwidth per channel (rcfm_tuner_levels: a range may mix bandwidths)
     rcfm::DeviceBuffer levels_part;   // rcfm_tuner_levels: float64 [count][segments] sums of channels split over workgroups
+    rcfm::DeviceBuffer power_part_sum, power_part_max;   // rcfm_tuner_power_spectrum: float64 sums / float32 maxima [cells][segments]
     rcfm::DeviceBuffer X;          // [halo | n bins | halo]: the halos repeat the far ends, so a channel's bins
     int64_t halo = 0;              //   base + d, |d| <= B/2 + 1, need no wrap-around (fused_passes.h)
     float2* ext = nullptr;         // rcfm_tuner_attach_spectrum: caller-owned storage of the same layout instead of X
@@ -246,6 +247,12 @@ struct rcfm_tuner_s {
         loaded_first = first;
         loaded_count = count;
     }
+    // the bins the storage holds since then: [held_first, held_first + held_bins) modulo n (held_bins = n: every bin)
+    int64_t held_first = 0, held_bins = 0;
+    void set_held(int64_t first_bin, int64_t nbins) {
+        held_first = first_bin;
+        held_bins = nbins;
+    }
 
     struct Band {
         rcfm::ResampleGeom geom;
@@ -268,6 +275,7 @@ struct rcfm_tuner_s {
     void require_loaded(int first, int count, const char* caller) const;
     void require_readable(int first, int count, const char* caller, int bw_code, const char* bw_msg) const;
     void levels(int first, int count, float* power, hipStream_t s);
+    void power_spectrum(int64_t s0, int64_t L, int64_t M, float* power, float* peak, hipStream_t s);
     void run(int first, int count, float2* out, hipStream_t s, float* theta = nullptr, int theta_pitch = 0,
              int narrow_mode = -1, bool envelope = false);
 };

@@ -155,6 +155,16 @@ void launch_ssb_tail(float* y, int64_t n, int batch, float level, hipStream_t st
 int level_segments(int64_t B);
 void launch_channel_levels(const float2* X, int64_t N, const int32_t* base, const int64_t* roll, const int32_t* bw,
                            int count, int max_segments, double* part, float* power, hipStream_t stream);
+// Wideband power spectrum (rcfm_tuner_power_spectrum): the span of L signed bins from s0 (bin s = X[s mod N]; it does not
+// wrap in frequency) is cut into M cells, cell m = span positions [floor(m L / M), floor((m + 1) L / M));
+// power[m] = sum, peak[m] = max of |X|^2 / N^2 over the cell, float64 inside, float32 out; either may be null.
+// Cells of at most 16 bins take a thread each, of at most 1024 bins a wave each; longer ones power_segments(L, M)
+// workgroups each -- all functions of (L, M) alone.  part_sum ([M][segments] float64) and part_max ([M][segments] float32),
+// needed when power_segments > 1, receive the segments' results and a finishing launch combines them in segment order:
+// bit-identical from run to run.
+int power_segments(int64_t L, int64_t M);
+void launch_power_spectrum(const float2* X, int64_t N, int64_t s0, int64_t L, int64_t M, double* part_sum, float* part_max,
+                           float* power, float* peak, hipStream_t stream);
 // Squelch (rcfm_squelch): open[c] = power[c] >= threshold[c] (false for NaN), one byte per channel (open may be null);
 // rows of closed channels of audio [count][row] float32 (may be null) := 0, rows of open channels untouched.
 void launch_squelch(const float* power, const float* threshold, int count, size_t row, float* audio, uint8_t* open,

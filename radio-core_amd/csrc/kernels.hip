@@ -1132,6 +1132,155 @@ __global__ __launch_bounds__(kThreads) void k_squelch(const float* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------
+// Wideband power spectrum (rcfm_tuner_power_spectrum)
+// ---------------------------------------------------------------------------
+
+constexpr int kPowerSegBins = 8192;        // bins per workgroup of a wide cell (64 KB of spectrum), as kLevelSegBins
+constexpr int kPowerThreadCellMax = 16;    // longest cell one thread sums alone
+constexpr int kPowerWaveCellMax = 1024;    // longest cell one wave sums alone
+
+// Cell m of a span of L bins cut into M cells starts at span position floor(m L / M) (64-bit: m, L < 2^31).
+// (One bin per cell, M = L, is the waterfall at full resolution: no 64-bit division for it.)
+__device__ __forceinline__ int64_t power_cell_edge(int64_t m, int64_t L, int64_t M) { return L == M ? m : m * L / M; }
+
+// Span position e is signed bin s0 + e, element (s0 + e) mod N of the spectrum.
+__device__ __forceinline__ float2 power_bin(const float2* __restrict__ X, int64_t N, int64_t s) { return X[s < 0 ? s + N : s]; }
+
+__device__ __forceinline__ void power_take(double& acc, double& mx, float re, float im) {
+    const double p = (double)re * re + (double)im * im;
+    acc += p;
+    mx = fmax(mx, p);
+}
+
+// Cell (or, TEAM = 256, segment blockIdx.y of cell blockIdx.x) per TEAM threads: sum and maximum of |X|^2 over the cell's
+// bins in float64, scaled by 1 / N^2 and rounded to float32 once.  TEAM is chosen from ceil(L / M) alone
+// (launch_power_spectrum), the segments of a cell from its length alone, so every sum has one order.
+//   TEAM = 1    thread m adds its cell's bins in ascending order (cells of at most kPowerThreadCellMax bins).
+//   TEAM = 64   wave m: lane-strided, then the shuffle tree.
+//   TEAM = 256  a workgroup, the k_channel_levels shape: the piece [a, b) of the span is one run of memory, or two where it
+//               crosses signed bin 0 (memory goes from element N - 1 to element 0 there).  A run is read in pairs of bins
+//               whose first has an even element index -- one 16-byte load per lane when X is 16-byte aligned (ALIGNED),
+//               the same two bins as 8-byte loads otherwise -- and thread 0 takes the single bins at its ends.  Per-thread
+//               strided float64, the waves' shuffle tree, the wave sums in order.  One segment per cell in the whole
+//               launch (gridDim.y == 1): the result goes straight out; else to part_sum / part_max [cell][segment].
+template <int TEAM, bool ALIGNED>
+__global__ __launch_bounds__(kThreads) void k_power_spectrum(const float2* __restrict__ X, int64_t N, int64_t s0, int64_t L,
+                                                             int64_t M, double inv_n2, double* __restrict__ part_sum,
+                                                             float* __restrict__ part_max, float* __restrict__ power,
+                                                             float* __restrict__ peak) {
+    const int tid = threadIdx.x;
+    double acc = 0.0, mx = 0.0;
+    if constexpr (TEAM == 1) {
+        const int64_t m = (int64_t)blockIdx.x * kThreads + tid;
+        if (m >= M) return;
+        const int64_t e1 = power_cell_edge(m + 1, L, M);
+        for (int64_t e = power_cell_edge(m, L, M); e < e1; ++e) {
+            const float2 v = power_bin(X, N, s0 + e);
+            power_take(acc, mx, v.x, v.y);
+        }
+        if (power != nullptr) power[m] = (float)(acc * inv_n2);
+        if (peak != nullptr) peak[m] = (float)(mx * inv_n2);
+    } else if constexpr (TEAM == 64) {
+        const int64_t m = (int64_t)blockIdx.x * (kThreads / 64) + (tid >> 6);
+        if (m >= M) return;   // (wave-uniform)
+        const int64_t e1 = power_cell_edge(m + 1, L, M);
+        for (int64_t e = power_cell_edge(m, L, M) + (tid & 63); e < e1; e += 64) {
+            const float2 v = power_bin(X, N, s0 + e);
+            power_take(acc, mx, v.x, v.y);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            acc += __shfl_down(acc, off, 64);
+            mx = fmax(mx, __shfl_down(mx, off, 64));
+        }
+        if ((tid & 63) != 0) return;
+        if (power != nullptr) power[m] = (float)(acc * inv_n2);
+        if (peak != nullptr) peak[m] = (float)(mx * inv_n2);
+    } else {
+        __shared__ double red[2][kThreads / 64];
+        const int64_t m = blockIdx.x;
+        const int seg = blockIdx.y;
+        const int64_t c0 = power_cell_edge(m, L, M), len = power_cell_edge(m + 1, L, M) - c0;
+        const int segs = (int)((len + kPowerSegBins - 1) / kPowerSegBins);
+        if (seg >= segs) return;   // (a cell one bin shorter than the longest: workgroup-uniform)
+        const int64_t per = (len + segs - 1) / segs;
+        const int64_t a = c0 + (int64_t)seg * per, b = min(c0 + len, a + per);
+        const int64_t z = min(max(-s0, a), b);   // span positions [a, z) are signed bins < 0, [z, b) the others
+        const int64_t start[2] = {s0 + a + N, s0 + z}, count[2] = {z - a, b - z};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const float2* run = X + start[r];
+            const int64_t n = count[r];
+            if (n <= 0) continue;
+            const int64_t head = start[r] & 1;   // 1: the first bin is the upper half of a 16-byte slot
+            const int64_t pairs = (n - head) / 2;
+            for (int64_t q = tid; q < pairs; q += kThreads) {
+                float4 v;
+                if constexpr (ALIGNED) {
+                    v = *reinterpret_cast<const float4*>(run + head + 2 * q);
+                } else {
+                    const float2 lo = run[head + 2 * q], hi = run[head + 2 * q + 1];
+                    v = make_float4(lo.x, lo.y, hi.x, hi.y);
+                }
+                power_take(acc, mx, v.x, v.y);
+                power_take(acc, mx, v.z, v.w);
+            }
+            if (tid == 0) {
+                if (head) power_take(acc, mx, run[0].x, run[0].y);
+                if ((n - head) & 1) power_take(acc, mx, run[n - 1].x, run[n - 1].y);
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            acc += __shfl_down(acc, off, 64);
+            mx = fmax(mx, __shfl_down(mx, off, 64));
+        }
+        if ((tid & 63) == 0) {
+            red[0][tid >> 6] = acc;
+            red[1][tid >> 6] = mx;
+        }
+        __syncthreads();
+        if (tid != 0) return;
+        double tot = 0.0, top = 0.0;
+        for (int w = 0; w < kThreads / 64; ++w) {
+            tot += red[0][w];
+            top = fmax(top, red[1][w]);
+        }
+        if (gridDim.y == 1) {
+            if (power != nullptr) power[m] = (float)(tot * inv_n2);
+            if (peak != nullptr) peak[m] = (float)(top * inv_n2);
+        } else {
+            part_sum[m * gridDim.y + seg] = tot;
+            part_max[m * gridDim.y + seg] = (float)(top * inv_n2);
+        }
+    }
+}
+
+// The finishing launch of split cells: wave m adds the segment sums of cell m lane-strided in segment order, then the
+// shuffle tree; the maximum of the float32 partial maxima is the rounded maximum (rounding is monotonic).
+__global__ __launch_bounds__(kThreads) void k_power_spectrum_finish(const double* __restrict__ part_sum,
+                                                                    const float* __restrict__ part_max, int64_t L, int64_t M,
+                                                                    int max_segments, double inv_n2,
+                                                                    float* __restrict__ power, float* __restrict__ peak) {
+    const int tid = threadIdx.x;
+    const int64_t m = (int64_t)blockIdx.x * (kThreads / 64) + (tid >> 6);
+    if (m >= M) return;   // (wave-uniform)
+    const int64_t len = power_cell_edge(m + 1, L, M) - power_cell_edge(m, L, M);
+    const int segs = (int)((len + kPowerSegBins - 1) / kPowerSegBins);
+    double tot = 0.0;
+    float top = 0.f;
+    for (int s = tid & 63; s < segs; s += 64) {
+        tot += part_sum[m * max_segments + s];
+        top = fmaxf(top, part_max[m * max_segments + s]);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        tot += __shfl_down(tot, off, 64);
+        top = fmaxf(top, __shfl_down(top, off, 64));
+    }
+    if ((tid & 63) != 0) return;
+    if (power != nullptr) power[m] = (float)(tot * inv_n2);
+    if (peak != nullptr) peak[m] = top;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1397,6 +1546,43 @@ void launch_channel_levels(const float2* X, int64_t N, const int32_t* base, cons
     if (max_segments > 1) {
         hipLaunchKernelGGL(k_channel_levels_finish, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
                            part, bw, count, max_segments, inv_n2, power);
+        RC_LAUNCH_CHECK();
+    }
+}
+
+int power_segments(int64_t L, int64_t M) {
+    const int64_t longest = (L + M - 1) / M;
+    return longest > kPowerWaveCellMax ? (int)((longest + kPowerSegBins - 1) / kPowerSegBins) : 1;
+}
+
+void launch_power_spectrum(const float2* X, int64_t N, int64_t s0, int64_t L, int64_t M, double* part_sum, float* part_max,
+                           float* power, float* peak, hipStream_t stream) {
+    if (M <= 0 || (power == nullptr && peak == nullptr)) return;
+    const int64_t longest = (L + M - 1) / M;
+    const int segs = power_segments(L, M);
+    RC_REQUIRE(segs <= 65535 && (segs == 1 || (part_sum != nullptr && part_max != nullptr)), RCFM_ERR_RUNTIME,
+               "bad segment count of the power spectrum");
+    const double inv_n2 = 1.0 / ((double)N * (double)N);
+    const int per_group = kThreads / 64;
+    if (longest <= kPowerThreadCellMax) {
+        hipLaunchKernelGGL((k_power_spectrum<1, false>), dim3((unsigned)((M + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                           stream, X, N, s0, L, M, inv_n2, part_sum, part_max, power, peak);
+    } else if (longest <= kPowerWaveCellMax) {
+        hipLaunchKernelGGL((k_power_spectrum<64, false>), dim3((unsigned)((M + per_group - 1) / per_group)), dim3(kThreads), 0,
+                           stream, X, N, s0, L, M, inv_n2, part_sum, part_max, power, peak);
+    } else {
+        const dim3 grid((unsigned)M, (unsigned)segs, 1);
+        if ((uintptr_t)X % 16 == 0)
+            hipLaunchKernelGGL((k_power_spectrum<kThreads, true>), grid, dim3(kThreads), 0, stream, X, N, s0, L, M, inv_n2,
+                               part_sum, part_max, power, peak);
+        else
+            hipLaunchKernelGGL((k_power_spectrum<kThreads, false>), grid, dim3(kThreads), 0, stream, X, N, s0, L, M, inv_n2,
+                               part_sum, part_max, power, peak);
+    }
+    RC_LAUNCH_CHECK();
+    if (segs > 1) {
+        hipLaunchKernelGGL(k_power_spectrum_finish, dim3((unsigned)((M + per_group - 1) / per_group)), dim3(kThreads), 0, stream,
+                           part_sum, part_max, L, M, segs, inv_n2, power, peak);
         RC_LAUNCH_CHECK();
     }
 }

@@ -88,6 +88,7 @@ void rcfm_tuner_s::adopt(int first, int count, hipStream_t s) {
         }
     }
     set_loaded(true, nb < n, first, count);
+    set_held(fb, nb);
 }
 
 // The bins [fb, fb + nb) of channels [first, first + count), which must be able to live in a storage of their own,
@@ -178,6 +179,28 @@ void rcfm_tuner_s::levels(int first, int count, float* power, hipStream_t s) {
     StageTimer tm(ST_LEVELS, s);
     launch_channel_levels(spectrum(), n, fast ? base_dev.as<int32_t>() + first : nullptr, roll_dev.as<int64_t>() + first,
                           bw_dev.as<int32_t>() + first, count, segs, segs > 1 ? levels_part.as<double>() : nullptr, power, s);
+}
+
+// power[m], peak[m] of cell m of the span [s0, s0 + L) of signed bins cut into M cells (include/rcfm.h,
+// rcfm_tuner_power_spectrum; the arguments are checked there).  Every bin of the span must be held: the span is one run of
+// elements, or two where it crosses signed bin 0, each inside [held_first, held_first + held_bins) modulo n.
+void rcfm_tuner_s::power_spectrum(int64_t s0, int64_t L, int64_t M, float* power, float* peak, hipStream_t s) {
+    RC_REQUIRE(loaded, RCFM_ERR_STATE, "rcfm_tuner_power_spectrum called before rcfm_tuner_load");
+    const int64_t z = std::min(std::max<int64_t>(-s0, 0), L);   // span positions [0, z) are signed bins < 0
+    const int64_t run[2][2] = {{s0 + n, z}, {s0 + z, L - z}};    // first element, length
+    for (auto& r : run) {
+        if (r[1] <= 0 || held_bins >= n) continue;
+        const int64_t off = ((r[0] - held_first) % n + n) % n;
+        RC_REQUIRE(off + r[1] <= held_bins, RCFM_ERR_STATE,
+                   "the span reaches bins the loaded, sharded or attached spectrum does not hold (rcfm_tuner_window)");
+    }
+    const int segs = power_segments(L, M);
+    if (segs > 1) {
+        power_part_sum.reserve(sizeof(double) * (size_t)M * segs);
+        power_part_max.reserve(sizeof(float) * (size_t)M * segs);
+    }
+    launch_power_spectrum(spectrum(), n, s0, L, M, segs > 1 ? power_part_sum.as<double>() : nullptr,
+                          segs > 1 ? power_part_max.as<float>() : nullptr, power, peak, s);
 }
 
 // theta != nullptr (phase_capable bands only): angle(x) / pi goes to theta [count][B] float32, out is unused;
@@ -305,6 +328,13 @@ int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream) {
         }
         t->set_loaded(true, t->forward_engine && (t->use_aligned() ? t->windowed_aligned : t->windowed), t->shard_first,
                       t->shard_count);
+        t->set_held(0, t->n);
+        if (t->loaded_windowed) {   // the rows the last pass of the plan that ran has stored
+            const bool al = t->use_aligned();
+            const FftRowWindow& w = al ? t->window_aligned : t->window;
+            const int64_t f0 = (al ? *t->forward_aligned : *t->forward_engine).row_length(), rows = t->n / f0;
+            t->set_held((int64_t)w.lo * f0, (((int64_t)w.hi - w.lo + rows) % rows + 1) * f0);
+        }
     });
 }
 
@@ -328,6 +358,18 @@ int rcfm_tuner_levels(rcfm_tuner_t t, int first, int count, void* power, void* s
         RC_REQUIRE(t && power, RCFM_ERR_ARG, "NULL argument");
         ArenaScope scope(t->arena);
         t->levels(first, count, static_cast<float*>(power), as_stream(stream));
+    });
+}
+
+int rcfm_tuner_power_spectrum(rcfm_tuner_t t, int64_t first_bin, int64_t nbins, int64_t cells, void* power, void* peak,
+                              void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(t && (power || peak), RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(nbins >= 1 && cells >= 1 && cells <= nbins, RCFM_ERR_ARG, "a span has at least one bin and 1 .. nbins cells");
+        RC_REQUIRE(first_bin >= -(t->n / 2) && nbins <= t->n && first_bin <= t->n - t->n / 2 - nbins, RCFM_ERR_ARG,
+                   "the span leaves the signed bins [-floor(n / 2), n - floor(n / 2))");
+        ArenaScope scope(t->arena);
+        t->power_spectrum(first_bin, nbins, cells, static_cast<float*>(power), static_cast<float*>(peak), as_stream(stream));
     });
 }
 
@@ -373,6 +415,7 @@ int rcfm_tuner_attach_spectrum(rcfm_tuner_t t, void* storage, int loaded_first, 
         int64_t fb = 0, nb = t->n;
         if (loaded_count > 0) t->bin_window(loaded_first, loaded_count, &fb, &nb);
         t->set_loaded(loaded_count > 0, nb < t->n, loaded_first, std::max(loaded_count, 0));
+        t->set_held(fb, nb);
     });
 }
 

@@ -12,6 +12,7 @@ from typing import List
 import numpy as np
 
 from radiocore._internal import Injector, hip
+from radiocore.tools import spectrum
 
 __all__ = ["Tuner", "Channel"]
 
@@ -293,6 +294,28 @@ class Tuner(Injector):
         power = hip.empty((count,), self._torch.float32)
         hip.check(self._lib.rcfm_tuner_levels(handle, first, count, hip.ptr(power), hip.stream()))
         return self._result(power, self._cuda and not numpy_output)
+
+    def power_spectrum(self, cells, f_lo=None, f_hi=None, peak=False, numpy_output: bool = True):
+        """What the band looks like between and around the channels (rcfm_tuner_power_spectrum; no reference
+        counterpart): the loaded spectrum from ``f_lo`` to ``f_hi`` Hz (half-open; None: the band's own end) cut into
+        ``cells`` cells of equal width to within one bin (``spectrum.cell_edges``), float32 [cells] -- the power in each
+        cell, linear, in the units of the input samples and of ``levels()``; over the whole band the cells add up to
+        ``mean(|x|**2)``.  peak=True returns ``(power, peak)``, peak being each cell's strongest bin: a narrow carrier
+        stays visible in a wide cell.  Valid after ``load`` / ``adopt``; under ``shard`` or an attached window only
+        the bins of ``window()`` are held and a span beyond them raises RuntimeError.  ValueError for an empty or
+        out-of-band span and for ``cells`` outside 1 .. the span's bins."""
+        if self._loaded_size is None:
+            raise RuntimeError("Tuner.power_spectrum called before Tuner.load")
+        s0, L = spectrum.span_bins(self._input_frequency, self._loaded_size, f_lo, f_hi)
+        cells = int(cells)
+        if cells < 1 or cells > L:
+            raise ValueError("a span of %d bins takes 1 .. %d cells, not %d" % (L, L, cells))
+        handle = self._ready()
+        out = [hip.empty((cells,), self._torch.float32) for _ in range(2 if peak else 1)]
+        hip.check(self._lib.rcfm_tuner_power_spectrum(handle, s0, L, cells, hip.ptr(out[0]), hip.ptr(out[1]) if peak else None,
+                                                      hip.stream()))
+        out = [self._result(o, self._cuda and not numpy_output) for o in out]
+        return (out[0], out[1]) if peak else out[0]
 
     def set_squelch(self, threshold=None):
         """Mute what is below a level: from now on ``run_all`` / ``run_each`` (and ``Lanes.submit``) compare every
