@@ -129,7 +129,10 @@ int rcfm_tuner_spectrum(rcfm_tuner_t t, void** X);
 /* ---- the spectrum as an object that can travel (multi-GPU: rotating FFT owner, radiocore/tools/sharding.py) ------
  * Tuner.load (tuner.py:126-138) keeps the spectrum in `self._buffer`; with channels sharded over G GPUs only ONE GPU
  * needs to run the wideband FFT of a given buffer, if it then hands every peer the bins that peer's channels read.
- *   spectrum_layout   storage = [halo | n bins | halo] complex64 (the halos repeat the far ends)
+ *   spectrum_layout   storage = [halo | n bins | halo] complex64 (the halos repeat the far ends: storage[0, halo) holds
+ *                     bins [n - halo, n), storage[halo + n, halo + n + halo) bins [0, halo)); halo <= n / 2 always, and
+ *                     halo = 0 -- no halos -- for a handle with a channel so wide that B / 2 + 2 bins, rounded up to
+ *                     whole 128-byte lines, exceed n / 2
  *   attach_spectrum   use caller-owned storage of that layout instead of the handle's own (NULL: back to its own);
  *                     loaded_count > 0 declares that it already holds the bins of channels [loaded_first, +count)
  *   window            the bins channels [first, first + count) read: [first_bin, first_bin + nbins) modulo n, whole

@@ -106,6 +106,7 @@ struct FftRowWindow {
     int lo, hi;
     // halo > 0 (batch 1, forward): outputs [0, halo) are also stored at out[n + g], outputs [n - halo, n) at
     // out[g - n] -- `out` must have `halo` elements of room on both sides.  lo = 0, hi = rows - 1 keeps every row.
+    // halo <= n / 2: an output belongs to one halo at most (the store decides with one comparison per side).
     int halo = 0;
 };
 

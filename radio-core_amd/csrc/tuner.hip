@@ -265,11 +265,13 @@ int rcfm_tuner_create(int64_t n, int nch, const int64_t* roll_host, const int32_
         }
         if (nch) t->roll_dev.upload(t->roll.data(), sizeof(int64_t) * nch);
         if (nch) t->bw_dev.upload(t->bw.data(), sizeof(int32_t) * nch);
-        // halo: whole 128-byte lines on both sides, wide enough for the widest channel
+        // halo: whole 128-byte lines on both sides, wide enough for the widest channel -- and no wider than n / 2, so
+        // that no bin belongs to both halos (FftRowWindow).  A handle with a channel wider than that keeps none: such a
+        // channel never takes a form that reads the halos (fast_gather_ok, fast_bins_ok).
         int64_t h = 0;
         for (int i = 0; i < nch; ++i) h = std::max<int64_t>(h, bw_host[i] / 2 + 2);
         h = (h + 15) / 16 * 16;
-        if (nch && h <= n && n + h < ((int64_t)1 << 31)) {
+        if (nch && 2 * h <= n && n + h < ((int64_t)1 << 31)) {
             t->halo = h;
             std::vector<int32_t> base(nch);
             for (int i = 0; i < nch; ++i) base[i] = (int32_t)((n - t->roll[i]) % n);
