@@ -43,7 +43,8 @@ extern "C" {
 #define RCFM_VERSION 102 /* 0.1.2: tooling entry points moved to rcfm_tools.h (same symbols), RCFM_OPT_GRAPH;
                             demodulator kinds RCFM_AM, RCFM_USB, RCFM_LSB (no new entry points);
                             rcfm_tuner_levels and rcfm_squelch added (new symbols only, nothing existing changed);
-                            rcfm_tuner_power_spectrum added (a new symbol only, nothing existing changed) */
+                            rcfm_tuner_power_spectrum added (a new symbol only, nothing existing changed);
+                            rcfm_tuner_carriers and rcfm_tuner_retune added (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -194,6 +195,41 @@ int rcfm_squelch(const void* power, const void* threshold, int count, size_t flo
  * first_bin = s0, nbins = L, cells = M; power, peak: [M] float32 device, either may be NULL */
 int rcfm_tuner_power_spectrum(rcfm_tuner_t t, int64_t first_bin, int64_t nbins, int64_t cells, void* power, void* peak,
                               void* stream);
+/* ---- carrier estimates and live retune (no reference counterpart) ----------------------------------------------------
+ * Where inside its channel a station sits.  For channel c (roll r, bandwidth B <= n) of the loaded spectrum X the channel's
+ * bins are the B signed offsets d = -floor(B/2) .. -floor(B/2) + B - 1 from the channel centre, bin d being element
+ * X[(d - r) mod n] -- the indexing of rcfm_tuner_levels; with one-second buffers d is Hz above the channel's centre
+ * frequency.  p_d = re^2 + im^2 of that element, formed in float64 from the float32 parts: no window weight and no Nyquist
+ * merge (a carrier finder must not depend on the gather form, and the Hann taper over n is flat across a channel).
+ *   peak_bin[i]   int32    the d of the largest p_d; on equal p_d the lowest d wins; a NaN p_d never wins
+ *   peak_power[i] float32  that p_d / n^2, scaled in float64 and rounded once: the units of rcfm_tuner_levels and
+ *                          rcfm_tuner_power_spectrum
+ *   centroid[i]   float32  S1 / S0
+ *   spread[i]     float32  sqrt(max(S2 / S0 - (S1 / S0)^2, 0))
+ * with S_k = sum of d^k p_d over the gated-in bins: bin d is gated in iff p_d >= G, G = (double)gate n n computed once on
+ * the host.  gate is power per bin in the units above, finite and >= 0; 0 takes every bin.  An ungated centroid of a weak
+ * station is pulled to 0 by the channel's noise; a host derives the gate from the floor density it already computes.
+ * When no bin is gated in (or S0 = 0) centroid = spread = 0.  The peak ignores the gate.
+ * Each output is [count] on the device and may be NULL, but not all four.  The channels of a range may differ in
+ * bandwidth.  Readiness as for rcfm_tuner_levels: RCFM_ERR_STATE before a load and for a channel outside the range that
+ * was loaded, sharded or attached as a window, RCFM_ERR_INDEX for a bad range.  RCFM_ERR_ARG (checked before any device
+ * call): NULL handle, all four outputs NULL, a negative or non-finite gate.
+ * Every sum has one order, a function of B alone, and there are no floating-point atomics: bit-identical from run to
+ * run, from stream to stream, and whichever outputs are NULL. */
+int rcfm_tuner_carriers(rcfm_tuner_t t, int first, int count, float gate, void* peak_bin, void* peak_power, void* centroid,
+                        void* spread, void* stream);
+/* New rolls for channels [first, first + count): roll_host[i] replaces the roll of channel first + i, reduced modulo n as
+ * rcfm_tuner_create reduces it.  Bandwidths, n, the halo, plans and storage stay as they are.  The host values are staged
+ * before the call returns (the caller's array may be freed at once) and the device tables are updated in order on
+ * `stream`: calls queued on that stream afterwards -- rcfm_tuner_run, rcfm_pipeline_run on every route, rcfm_tuner_levels,
+ * rcfm_tuner_carriers -- see the new rolls.  The host must not have calls of this handle in flight on OTHER streams.
+ * After a plain load every bin is held: the handle stays loaded and the same buffer can be run again at once.  Where the
+ * storage holds a window only (a sharded load, rcfm_tuner_adopt, rcfm_tuner_attach_spectrum with loaded channels) the held
+ * bins were chosen for the old rolls: the handle becomes not-loaded and reads return RCFM_ERR_STATE until the next
+ * rcfm_tuner_load or rcfm_tuner_adopt; a declared shard (rcfm_tuner_shard) follows the new rolls from that load on.
+ * RCFM_ERR_STATE while a window storage is attached (rcfm_tuner_attach_window): its layout was computed from the old
+ * rolls.  RCFM_ERR_INDEX for a bad range, RCFM_ERR_ARG for a NULL handle or NULL rolls with count > 0. */
+int rcfm_tuner_retune(rcfm_tuner_t t, int first, int count, const int64_t* roll_host, void* stream);
 int rcfm_tuner_destroy(rcfm_tuner_t t);
 
 /* ---- demodulators (radiocore/analog/{fm,mfm,wbfm}.py) --------------------- */

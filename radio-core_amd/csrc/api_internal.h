@@ -192,7 +192,14 @@ inline void require_channels(int first, int count, int n) {
 
 struct rcfm_tuner_s {
     rcfm::Arena* arena = rcfm::arena_enter_handle();   // rcfm_arena_bind at creation: every workspace of this handle, for its whole life
-    ~rcfm_tuner_s() { rcfm::arena_leave_handle(arena); }   // (the members drop their pieces after this body)
+    ~rcfm_tuner_s() {                                       // (the members drop their pieces after this body)
+        if (stage_done) {
+            (void)hipEventSynchronize(stage_done);   // a retune's copies may still read the staging memory
+            (void)hipEventDestroy(stage_done);
+        }
+        if (stage) (void)hipHostFree(stage);
+        rcfm::arena_leave_handle(arena);
+    }
     int opt_narrow = rcfm::kNarrowDefault;  // RCFM_TUNER_OPT_NARROW_TILES (rcfm_pipeline_run passes the demodulator's setting)
     int64_t n = 0;
     int nch = 0;
@@ -200,8 +207,14 @@ struct rcfm_tuner_s {
     std::vector<int32_t> bw;
     rcfm::DeviceBuffer roll_dev;
     rcfm::DeviceBuffer base_dev;   // int32 (n - roll) mod n per channel: start of the channel in the haloed spectrum
+    // rcfm_tuner_retune: pinned host copy of the new rolls and bases on their way to the device; stage_done is recorded
+    // behind the copies, and the next retune waits for it before it overwrites the staging memory
+    void* stage = nullptr;
+    size_t stage_bytes = 0;
+    hipEvent_t stage_done = nullptr;
     rcfm::DeviceBuffer bw_dev;     // int32 bandwidth per channel (rcfm_tuner_levels: a range may mix bandwidths)
     rcfm::DeviceBuffer levels_part;   // rcfm_tuner_levels: float64 [count][segments] sums of channels split over workgroups
+    rcfm::DeviceBuffer carriers_part; // rcfm_tuner_carriers: CarrierPart [count][segments] of channels split over workgroups
     rcfm::DeviceBuffer power_part_sum, power_part_max;   // rcfm_tuner_power_spectrum: float64 sums / float32 maxima [cells][segments]
     rcfm::DeviceBuffer X;          // [halo | n bins | halo]: the halos repeat the far ends, so a channel's bins
     int64_t halo = 0;              //   base + d, |d| <= B/2 + 1, need no wrap-around (fused_passes.h)
@@ -269,12 +282,16 @@ struct rcfm_tuner_s {
     void window_storage(int first, int count, int64_t* fb, int64_t* nb) const;
     bool fast_gather_ok(int first);
     bool fast_bins_ok(int32_t B) const;
+    bool halo_run_ok(int32_t B) const;
     bool phase_capable(int first);
     int band_row_length(int first);
     bool band_two_pass(int first);
     void require_loaded(int first, int count, const char* caller) const;
     void require_readable(int first, int count, const char* caller, int bw_code, const char* bw_msg) const;
     void levels(int first, int count, float* power, hipStream_t s);
+    void carriers(int first, int count, double gate_n2, int32_t* peak_bin, float* peak_power, float* centroid, float* spread,
+                  hipStream_t s);
+    void retune(int first, int count, const int64_t* roll_host, hipStream_t s);
     void power_spectrum(int64_t s0, int64_t L, int64_t M, float* power, float* peak, hipStream_t s);
     void run(int first, int count, float2* out, hipStream_t s, float* theta = nullptr, int theta_pitch = 0,
              int narrow_mode = -1, bool envelope = false);

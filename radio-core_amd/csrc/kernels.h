@@ -155,6 +155,23 @@ void launch_ssb_tail(float* y, int64_t n, int batch, float level, hipStream_t st
 int level_segments(int64_t B);
 void launch_channel_levels(const float2* X, int64_t N, const int32_t* base, const int64_t* roll, const int32_t* bw,
                            int count, int max_segments, double* part, float* power, hipStream_t stream);
+// Carrier estimates (rcfm_tuner_carriers): over the B_c bins of channel c at signed offsets d = -(B_c / 2) ..
+// -(B_c / 2) + B_c - 1 of its centre, p_d = |X[(d - roll[c]) mod N]|^2 in float64, unweighted:
+//   peak_bin[c] = the d of the largest p_d (the lowest d among equals; a NaN never wins), peak_power[c] = that p_d / N^2,
+//   centroid[c] = S1 / S0, spread[c] = sqrt(max(S2 / S0 - (S1 / S0)^2, 0)), S_k = sum of d^k p_d over the bins with
+//   p_d >= gate_n2 (both 0 when S0 is not positive).  Any output may be null.
+//   base != nullptr (fast form): X is haloed, the run of channel c is X[base[c] - B_c / 2 .. ] with no wrap-around, read
+//     16 bytes per lane;  base == nullptr (general form): bin (d - roll[c]) mod N per element, 64-bit.
+// Segments as launch_channel_levels: level_segments(B_c) workgroups per channel; part ([count][max segments], needed when
+// any channel has more than one) receives their records and a finishing launch combines them in segment order:
+// bit-identical from run to run, and whichever outputs are null.
+struct CarrierPart {
+    double s0, s1, s2, mx;
+    int32_t md, pad;
+};
+void launch_channel_carriers(const float2* X, int64_t N, const int32_t* base, const int64_t* roll, const int32_t* bw,
+                             int count, int max_segments, double gate_n2, CarrierPart* part, int32_t* peak_bin,
+                             float* peak_power, float* centroid, float* spread, hipStream_t stream);
 // Wideband power spectrum (rcfm_tuner_power_spectrum): the span of L signed bins from s0 (bin s = X[s mod N]; it does not
 // wrap in frequency) is cut into M cells, cell m = span positions [floor(m L / M), floor((m + 1) L / M));
 // power[m] = sum, peak[m] = max of |X|^2 / N^2 over the cell, float64 inside, float32 out; either may be null.

@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 
+#include <climits>
 #include <cmath>
 #include "device_math.h"
 
@@ -1104,6 +1105,157 @@ __global__ __launch_bounds__(kThreads) void k_channel_levels_finish(const double
     power[c] = (float)(tot * inv_n2);
 }
 
+// ---------------------------------------------------------------------------
+// Carrier estimates (rcfm_tuner_carriers)
+// ---------------------------------------------------------------------------
+
+// What a thread, a wave, a workgroup and a channel carry: the gated moments S0, S1, S2 of p_d = |X|^2 over the signed
+// offsets d of the channel centre, and the largest p_d with its d.  mx = -1, md = INT_MAX: nothing seen yet (p_d >= 0; a
+// NaN p_d compares false both ways and never gets in).
+struct CarrierAcc {
+    double s0, s1, s2, mx;
+    int md;
+};
+
+__device__ __forceinline__ void carrier_take(CarrierAcc& a, float re, float im, int d, double G) {
+    const double p = (double)re * re + (double)im * im;
+    if (p >= G) {
+        const double dd = (double)d;
+        a.s0 += p;
+        a.s1 += dd * p;
+        a.s2 += dd * dd * p;
+    }
+    if (p > a.mx || (p == a.mx && d < a.md)) {
+        a.mx = p;
+        a.md = d;
+    }
+}
+
+// a := a (+) b, b the LATER part in the fixed order of the sums.  The maximum's rule -- larger p, or equal p and lower d
+// -- is the same at every level, so it is associative and the result does not depend on how the bins were dealt out.
+__device__ __forceinline__ void carrier_merge(CarrierAcc& a, double s0, double s1, double s2, double mx, int md) {
+    a.s0 += s0;
+    a.s1 += s1;
+    a.s2 += s2;
+    if (mx > a.mx || (mx == a.mx && md < a.md)) {
+        a.mx = mx;
+        a.md = md;
+    }
+}
+
+// The four results of a channel from its sums; an output that is null is not stored.  A channel without a single
+// comparable p_d (all NaN) reports its first bin and NaN.
+__device__ __forceinline__ void carrier_store(int c, const CarrierAcc& a, int dlo, double inv_n2, int32_t* __restrict__ peak_bin,
+                                              float* __restrict__ peak_power, float* __restrict__ centroid,
+                                              float* __restrict__ spread) {
+    const bool seen = a.mx >= 0.0;
+    if (peak_bin != nullptr) peak_bin[c] = seen ? a.md : dlo;
+    if (peak_power != nullptr) peak_power[c] = seen ? (float)(a.mx * inv_n2) : __builtin_nanf("");
+    const bool any = a.s0 > 0.0;
+    const double m = any ? a.s1 / a.s0 : 0.0;
+    if (centroid != nullptr) centroid[c] = (float)m;
+    if (spread != nullptr) spread[c] = any ? (float)sqrt(fmax(a.s2 / a.s0 - m * m, 0.0)) : 0.f;
+}
+
+// Carrier estimate of channel blockIdx.x, segment blockIdx.y (kernels.h, launch_channel_carriers).  The channel's B bins
+// sit at signed offsets d = -(B / 2) .. -(B / 2) + B - 1 of its centre: no window weight, no Nyquist merge.
+// FAST: the run is X[base - B / 2 ...] of the haloed spectrum, read as k_channel_levels reads its run: the start is 8- or
+// 16-byte aligned (the parity of base differs per channel), thread 0 of segment 0 takes the head element of a misaligned
+// run and the odd one at the end, everything between is pairs of bins, one 16-byte load per lane, the segments splitting
+// the pairs evenly.  !FAST: element e of the run is bin (d - roll) mod N, one 8-byte load per lane.
+// Per-thread strided float64 sums and maximum, the waves' shuffle tree, the wave results in wave order.  One segment per
+// channel in the whole launch (gridDim.y == 1): the results go straight out; else the sums go to part[c][segment].
+template <bool FAST>
+__global__ __launch_bounds__(kThreads) void k_channel_carriers(const float2* __restrict__ X, int64_t N,
+                                                               const int32_t* __restrict__ base,
+                                                               const int64_t* __restrict__ roll,
+                                                               const int32_t* __restrict__ bw, double G, double inv_n2,
+                                                               CarrierPart* __restrict__ part,
+                                                               int32_t* __restrict__ peak_bin,
+                                                               float* __restrict__ peak_power,
+                                                               float* __restrict__ centroid, float* __restrict__ spread) {
+    __shared__ double red[4][kThreads / 64];
+    __shared__ int red_d[kThreads / 64];
+    const int c = blockIdx.x, seg = blockIdx.y, tid = threadIdx.x;
+    const int B = bw[c];
+    const int segs = min(kLevelMaxSegs, (B + kLevelSegBins - 1) / kLevelSegBins);
+    if (seg >= segs) return;   // (a narrower channel of a mixed range: workgroup-uniform)
+    const int dlo = -(B / 2);
+    CarrierAcc acc{0.0, 0.0, 0.0, -1.0, INT_MAX};
+    if (FAST) {
+        const float2* run = X + ((int64_t)base[c] + dlo);
+        const int head = (int)(((uintptr_t)run >> 3) & 1);   // 1: the first bin is the upper half of a 16-byte slot
+        const int pairs = (B - head) / 2;
+        const int per = (pairs + segs - 1) / segs;
+        const int q1 = min(pairs, (seg + 1) * per);
+        const float4* run4 = reinterpret_cast<const float4*>(run + head);
+        for (int q = seg * per + tid; q < q1; q += kThreads) {
+            const float4 v = run4[q];
+            const int d = dlo + head + 2 * q;
+            carrier_take(acc, v.x, v.y, d, G);
+            carrier_take(acc, v.z, v.w, d + 1, G);
+        }
+        if (seg == 0 && tid == 0) {
+            if (head) carrier_take(acc, run[0].x, run[0].y, dlo, G);
+            if ((B - head) & 1) carrier_take(acc, run[B - 1].x, run[B - 1].y, dlo + B - 1, G);
+        }
+    } else {
+        const int64_t r = roll[c];
+        const int per = (B + segs - 1) / segs;
+        const int e1 = min(B, (seg + 1) * per);
+        for (int e = seg * per + tid; e < e1; e += kThreads) {
+            int64_t i = ((int64_t)(dlo + e) - r) % N;   // (d - r) mod N, |d| <= N / 2, r in [0, N)
+            const float2 v = X[i < 0 ? i + N : i];
+            carrier_take(acc, v.x, v.y, dlo + e, G);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        carrier_merge(acc, __shfl_down(acc.s0, off, 64), __shfl_down(acc.s1, off, 64), __shfl_down(acc.s2, off, 64),
+                      __shfl_down(acc.mx, off, 64), __shfl_down(acc.md, off, 64));
+    if ((tid & 63) == 0) {
+        const int w = tid >> 6;
+        red[0][w] = acc.s0;
+        red[1][w] = acc.s1;
+        red[2][w] = acc.s2;
+        red[3][w] = acc.mx;
+        red_d[w] = acc.md;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    for (int w = 1; w < kThreads / 64; ++w) carrier_merge(acc, red[0][w], red[1][w], red[2][w], red[3][w], red_d[w]);
+    if (gridDim.y == 1) {
+        carrier_store(c, acc, dlo, inv_n2, peak_bin, peak_power, centroid, spread);
+    } else {
+        CarrierPart& o = part[(int64_t)c * gridDim.y + seg];
+        o.s0 = acc.s0;
+        o.s1 = acc.s1;
+        o.s2 = acc.s2;
+        o.mx = acc.mx;
+        o.md = acc.md;
+        o.pad = 0;
+    }
+}
+
+// The finishing launch of a split k_channel_carriers: one thread per channel combines its segments in segment order.
+__global__ __launch_bounds__(kThreads) void k_channel_carriers_finish(const CarrierPart* __restrict__ part,
+                                                                      const int32_t* __restrict__ bw, int count,
+                                                                      int max_segments, double inv_n2,
+                                                                      int32_t* __restrict__ peak_bin,
+                                                                      float* __restrict__ peak_power,
+                                                                      float* __restrict__ centroid,
+                                                                      float* __restrict__ spread) {
+    const int c = blockIdx.x * kThreads + threadIdx.x;
+    if (c >= count) return;
+    const int B = bw[c];
+    const int segs = min(kLevelMaxSegs, (B + kLevelSegBins - 1) / kLevelSegBins);
+    CarrierAcc acc{0.0, 0.0, 0.0, -1.0, INT_MAX};
+    for (int s = 0; s < segs; ++s) {
+        const CarrierPart& p = part[(int64_t)c * max_segments + s];
+        carrier_merge(acc, p.s0, p.s1, p.s2, p.mx, p.md);
+    }
+    carrier_store(c, acc, -(B / 2), inv_n2, peak_bin, peak_power, centroid, spread);
+}
+
 constexpr int kSquelchSeg = 16 * kThreads;   // floats of a row per workgroup: four 16-byte stores per lane
 
 // Squelch on channel blockIdx.x: open = power >= threshold (false for NaN), written as one byte by the row's first
@@ -1546,6 +1698,28 @@ void launch_channel_levels(const float2* X, int64_t N, const int32_t* base, cons
     if (max_segments > 1) {
         hipLaunchKernelGGL(k_channel_levels_finish, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
                            part, bw, count, max_segments, inv_n2, power);
+        RC_LAUNCH_CHECK();
+    }
+}
+
+void launch_channel_carriers(const float2* X, int64_t N, const int32_t* base, const int64_t* roll, const int32_t* bw,
+                             int count, int max_segments, double gate_n2, CarrierPart* part, int32_t* peak_bin,
+                             float* peak_power, float* centroid, float* spread, hipStream_t stream) {
+    if (count <= 0) return;
+    RC_REQUIRE(max_segments >= 1 && max_segments <= kLevelMaxSegs && (max_segments == 1 || part != nullptr), RCFM_ERR_RUNTIME,
+               "bad segment count of the carrier sums");
+    const double inv_n2 = 1.0 / ((double)N * (double)N);
+    const dim3 grid((unsigned)count, (unsigned)max_segments, 1);
+    if (base != nullptr)
+        hipLaunchKernelGGL(k_channel_carriers<true>, grid, dim3(kThreads), 0, stream, X, N, base, roll, bw, gate_n2, inv_n2,
+                           part, peak_bin, peak_power, centroid, spread);
+    else
+        hipLaunchKernelGGL(k_channel_carriers<false>, grid, dim3(kThreads), 0, stream, X, N, base, roll, bw, gate_n2, inv_n2,
+                           part, peak_bin, peak_power, centroid, spread);
+    RC_LAUNCH_CHECK();
+    if (max_segments > 1) {
+        hipLaunchKernelGGL(k_channel_carriers_finish, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                           stream, part, bw, count, max_segments, inv_n2, peak_bin, peak_power, centroid, spread);
         RC_LAUNCH_CHECK();
     }
 }

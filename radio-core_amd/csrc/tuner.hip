@@ -3,6 +3,8 @@
 
 #include "api_internal.h"
 
+#include <cmath>
+
 using namespace rcfm;
 
 // Rows of the spectrum (row = n_1 consecutive bins, n_1 = the forward plan's first pass length) that channels
@@ -134,6 +136,10 @@ bool rcfm_tuner_s::fast_bins_ok(int32_t B) const {
     return halo > 0 && series && halo >= B / 2 + 1 && B <= n;
 }
 
+// The B bins d = -(B / 2) .. of a channel as one run of the haloed spectrum, unweighted (carriers()): the halo reaches
+// them, nothing more -- no window is evaluated, so the series precondition of fast_bins_ok does not apply.
+bool rcfm_tuner_s::halo_run_ok(int32_t B) const { return halo > 0 && halo >= B / 2 + 1 && B <= n; }
+
 // Can run() leave angle(x) / pi instead of x for this channel's band?  (engine path only)
 bool rcfm_tuner_s::phase_capable(int first) { return first >= 0 && first < nch && band(bw[first]).engine != nullptr; }
 
@@ -179,6 +185,60 @@ void rcfm_tuner_s::levels(int first, int count, float* power, hipStream_t s) {
     StageTimer tm(ST_LEVELS, s);
     launch_channel_levels(spectrum(), n, fast ? base_dev.as<int32_t>() + first : nullptr, roll_dev.as<int64_t>() + first,
                           bw_dev.as<int32_t>() + first, count, segs, segs > 1 ? levels_part.as<double>() : nullptr, power, s);
+}
+
+// The carrier estimates of channels [first, first + count) (include/rcfm.h, rcfm_tuner_carriers; the arguments are checked
+// there): one read of each channel's bins, unweighted.  The fast form needs every channel of the range to pass
+// halo_run_ok; segments and their order as levels().  gate_n2 = gate n^2, the gate in units of |X|^2.
+void rcfm_tuner_s::carriers(int first, int count, double gate_n2, int32_t* peak_bin, float* peak_power, float* centroid,
+                            float* spread, hipStream_t s) {
+    require_channels(first, count, nch);
+    require_loaded(first, count, "rcfm_tuner_carriers");
+    if (count == 0) return;
+    bool fast = true;
+    int segs = 1;
+    for (int c = first; c < first + count; ++c) {
+        RC_REQUIRE(bw[c] <= n, RCFM_ERR_ARG, "channel bandwidth exceeds the input bandwidth");
+        fast = fast && halo_run_ok(bw[c]);
+        segs = std::max(segs, level_segments(bw[c]));
+    }
+    if (segs > 1) carriers_part.reserve(sizeof(CarrierPart) * (size_t)count * segs);
+    launch_channel_carriers(spectrum(), n, fast ? base_dev.as<int32_t>() + first : nullptr, roll_dev.as<int64_t>() + first,
+                            bw_dev.as<int32_t>() + first, count, segs, gate_n2,
+                            segs > 1 ? carriers_part.as<CarrierPart>() : nullptr, peak_bin, peak_power, centroid, spread, s);
+}
+
+// New rolls for channels [first, first + count) (include/rcfm.h, rcfm_tuner_retune).  The tables travel through pinned
+// staging memory of the handle, so the caller's array is free at once and the copies are plain stream work.
+void rcfm_tuner_s::retune(int first, int count, const int64_t* roll_host, hipStream_t s) {
+    require_channels(first, count, nch);
+    RC_REQUIRE(!ext_window, RCFM_ERR_STATE,
+               "a window is attached: its layout was computed from the old rolls (rcfm_tuner_attach_window)");
+    if (count == 0) return;
+    const size_t roll_bytes = sizeof(int64_t) * (size_t)count, base_bytes = halo > 0 ? sizeof(int32_t) * (size_t)count : 0;
+    if (stage_done) RC_HIP(hipEventSynchronize(stage_done));   // the previous retune's copies have read the staging memory
+    else RC_HIP(hipEventCreateWithFlags(&stage_done, hipEventDisableTiming));
+    if (stage_bytes < roll_bytes + base_bytes) {
+        if (stage) RC_HIP(hipHostFree(stage));
+        stage = nullptr;
+        stage_bytes = 0;
+        RC_HIP(hipHostMalloc(&stage, roll_bytes + base_bytes, hipHostMallocDefault));
+        stage_bytes = roll_bytes + base_bytes;
+    }
+    int64_t* roll_stage = static_cast<int64_t*>(stage);
+    int32_t* base_stage = reinterpret_cast<int32_t*>(roll_stage + count);
+    for (int i = 0; i < count; ++i) {
+        int64_t r = roll_host[i] % n;
+        if (r < 0) r += n;
+        roll[first + i] = roll_stage[i] = r;
+        if (halo > 0) base_stage[i] = (int32_t)((n - r) % n);
+    }
+    RC_HIP(hipMemcpyAsync(roll_dev.as<int64_t>() + first, roll_stage, roll_bytes, hipMemcpyHostToDevice, s));
+    if (halo > 0) RC_HIP(hipMemcpyAsync(base_dev.as<int32_t>() + first, base_stage, base_bytes, hipMemcpyHostToDevice, s));
+    RC_HIP(hipEventRecord(stage_done, s));
+    // the rows a sharded load keeps follow the rolls; a storage that holds a window only holds it for the old ones
+    if (shard_count > 0) shard(shard_first, shard_count);
+    if (loaded && (loaded_windowed || held_bins < n)) set_loaded(false, false, loaded_first, 0);
 }
 
 // power[m], peak[m] of cell m of the span [s0, s0 + L) of signed bins cut into M cells (include/rcfm.h,
@@ -360,6 +420,27 @@ int rcfm_tuner_levels(rcfm_tuner_t t, int first, int count, void* power, void* s
         RC_REQUIRE(t && power, RCFM_ERR_ARG, "NULL argument");
         ArenaScope scope(t->arena);
         t->levels(first, count, static_cast<float*>(power), as_stream(stream));
+    });
+}
+
+int rcfm_tuner_carriers(rcfm_tuner_t t, int first, int count, float gate, void* peak_bin, void* peak_power, void* centroid,
+                        void* spread, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(t != nullptr, RCFM_ERR_ARG, "NULL handle");
+        RC_REQUIRE(peak_bin || peak_power || centroid || spread, RCFM_ERR_ARG, "all four outputs are NULL");
+        RC_REQUIRE(std::isfinite(gate) && gate >= 0.f, RCFM_ERR_ARG, "the gate must be finite and >= 0");
+        ArenaScope scope(t->arena);
+        t->carriers(first, count, (double)gate * (double)t->n * (double)t->n, static_cast<int32_t*>(peak_bin),
+                    static_cast<float*>(peak_power), static_cast<float*>(centroid), static_cast<float*>(spread),
+                    as_stream(stream));
+    });
+}
+
+int rcfm_tuner_retune(rcfm_tuner_t t, int first, int count, const int64_t* roll_host, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(t != nullptr, RCFM_ERR_ARG, "NULL handle");
+        RC_REQUIRE(count <= 0 || roll_host != nullptr, RCFM_ERR_ARG, "roll is NULL");
+        t->retune(first, count, roll_host, as_stream(stream));
     });
 }
 

@@ -69,6 +69,8 @@ SIGNATURES = {
     "rcfm_tuner_levels": [_vp, _i, _i, _vp, _vp],
     "rcfm_squelch": [_vp, _vp, _i, _sz, _vp, _vp, _vp],
     "rcfm_tuner_power_spectrum": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
+    "rcfm_tuner_carriers": [_vp, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp],
+    "rcfm_tuner_retune": [_vp, _i, _i, ctypes.POINTER(_i64), _vp],
     "rcfm_tuner_destroy": [_vp],
     "rcfm_demod_create": [_i, _i, _i, _i, _dbl, _i, ctypes.POINTER(_vp)],
     "rcfm_demod_run": [_vp, _i, _i, _vp, _vp, _vp],

@@ -8,6 +8,7 @@ from radiocore.tools.ringbuffer import *
 from radiocore.tools.sharding import *
 from radiocore.tools.wire import *
 from radiocore.tools.squelch import *
+from radiocore.tools.afc import *
 from radiocore.tools.spectrum import *
 from radiocore.tools.feeder import *
 from radiocore.tools.lanes import *

@@ -71,6 +71,8 @@ class Tuner(Injector):
         self._squelch = None       # set_squelch: None (off) or float32 thresholds, 0-d (every channel) or [len(channels())]
         self._squelch_dev = None   # (channel-list version, device float32 [C]): rebuilt when either changes
         self._open = None          # device uint8 masks of the last run_all / run_each, one per launch group
+        self._fine = None          # retune: None or int64 [len(channels())] bins each channel was moved up (a new object per retune)
+        self._handle_fine = None   # the _fine the device handle's rolls were last set from
 
     @property
     def input_frequency(self) -> float:
@@ -121,6 +123,7 @@ class Tuner(Injector):
         # differ from the running total in the last bit.  Channel objects are not expected to change after add_channel
         # (the device handle is keyed by the list's version, not by its contents).
         self._version += 1
+        self._fine = None          # the fine-tune belongs to the channel list's version
         if added is not None and self._lo is not None:
             self._lo = min(self._lo, added.lower_frequency)
             self._hi = max(self._hi, added.higher_frequency)
@@ -144,20 +147,30 @@ class Tuner(Injector):
         key = (n, self._version)
         if key != self._handle_key:
             if self._abi_arrays is None or self._abi_arrays[0] != self._version:
-                rolls = [int(self._input_frequency - ch.center_frequency) for ch in self._bounds]
                 bws = [int(ch.bandwidth) for ch in self._bounds]
-                self._abi_arrays = (self._version, (ctypes.c_int64 * len(rolls))(*rolls),
-                                    (ctypes.c_int32 * len(bws))(*bws))
+                self._abi_arrays = (self._version, self._rolls(self._fine), (ctypes.c_int32 * len(bws))(*bws))
             _, roll_a, bw_a = self._abi_arrays
             h = ctypes.c_void_p()
             with hip.bound(self._arena):
                 hip.check(self._lib.rcfm_tuner_create(n, len(self._bounds), roll_a, bw_a, ctypes.byref(h)))
             self._handle = hip.Handle(h, self._lib.rcfm_tuner_destroy)
             self._handle_key = key
+            self._handle_fine = self._fine
             self._loaded_size = None
             if self._shard is not None:
                 hip.check(self._lib.rcfm_tuner_shard(h, self._shard[0], self._shard[1]))
         return self._handle.value
+
+    def _rolls(self, fine):
+        # roll[c] = int(f_in - f_c) (tuner.py:152) minus the bins the channel was moved up by retune
+        rolls = [int(self._input_frequency - ch.center_frequency) for ch in self._bounds]
+        if fine is not None:
+            rolls = [r - int(k) for r, k in zip(rolls, fine)]
+        return (ctypes.c_int64 * len(rolls))(*rolls)
+
+    def _apply_fine(self, handle, fine):
+        hip.check(self._lib.rcfm_tuner_retune(handle, 0, len(self._bounds), self._rolls(fine), hip.stream()))
+        self._handle_fine = fine
 
     def shard(self, first, count):
         """Multi-GPU only (no reference counterpart): this process will run channels
@@ -177,6 +190,8 @@ class Tuner(Injector):
         x = hip.to_device(input_signal, self._torch.complex64)
         n = int(x.shape[0])
         h = self._device_tuner(n)
+        if self._handle_fine is not self._fine:        # a lane that follows the base tuner's retune, on its own stream
+            self._apply_fine(h, self._fine)
         if whole and self._shard is not None:
             hip.check(self._lib.rcfm_tuner_shard(h, 0, len(self._bounds)))
             try:
@@ -294,6 +309,46 @@ class Tuner(Injector):
         power = hip.empty((count,), self._torch.float32)
         hip.check(self._lib.rcfm_tuner_levels(handle, first, count, hip.ptr(power), hip.stream()))
         return self._result(power, self._cuda and not numpy_output)
+
+    # ---- carrier estimates and live retune (rcfm_tuner_carriers / rcfm_tuner_retune; no reference counterpart) --------
+
+    def carriers(self, gate: float = 0.0, numpy_output: bool = True):
+        """Where inside its channel each station sits: ``(peak_bin, peak_power, centroid, spread)``, one array of
+        [count] each for every channel (of the shard's range after ``shard``), read from the loaded spectrum without the
+        inverse FFT.  Offsets are bins from the channel centre -- Hz with one-second buffers: ``peak_bin`` (int32) the
+        strongest bin, ``peak_power`` its power in the units of ``levels()`` per bin, ``centroid`` and ``spread`` the
+        power-weighted mean and standard deviation over the bins whose power is at least ``gate`` (same units; 0 takes
+        every bin, and a weak station's centroid is then pulled to 0 by the noise).  Valid after ``load`` / ``adopt``."""
+        handle = self._ready()
+        _, first, count = self._launch_plan()
+        t = self._torch
+        out = [hip.empty((count,), dt) for dt in (t.int32, t.float32, t.float32, t.float32)]
+        hip.check(self._lib.rcfm_tuner_carriers(handle, first, count, float(gate), *[hip.ptr(o) for o in out], hip.stream()))
+        return tuple(self._result(o, self._cuda and not numpy_output) for o in out)
+
+    def retune(self, offsets):
+        """Move channel c up by ``offsets[c]`` bins (Hz with one-second buffers; a scalar moves every channel), on top of
+        earlier retunes: a carrier that ``carriers()`` reported at ``peak_bin = k`` reads 0 after ``retune(k)``.  The
+        device handle keeps its spectrum, plans and storage; after a plain ``load`` the same buffer can be run again at
+        once, after a sharded load or ``adopt`` the next ``load`` / ``adopt`` must come first (RuntimeError until then),
+        and while a window is attached the call is refused.  ``Channel`` objects and the input geometry do not change;
+        ``add_channel`` and ``reset`` clear the fine-tune, ``fine_tune()`` returns it."""
+        a = np.asarray(offsets)
+        if a.dtype.kind not in "iu":
+            if a.dtype.kind != "f" or not np.all(a == np.round(a)):
+                raise ValueError("retune offsets are whole numbers of bins")
+        C = len(self._bounds)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != C):
+            raise ValueError("retune offsets: a scalar or one per channel (%d)" % C)
+        fine = self.fine_tune() + np.broadcast_to(a, (C,)).astype(np.int64)      # (a new object per retune: lanes compare by identity)
+        if self._handle is not None and self._handle_key[1] == self._version:
+            self._apply_fine(self._handle.value, fine)
+        self._fine = fine
+        self._abi_arrays = None
+
+    def fine_tune(self):
+        """int64 [len(channels())]: the bins every channel has been moved up by ``retune`` since the channel list last changed."""
+        return np.zeros(len(self._bounds), np.int64) if self._fine is None else self._fine.copy()
 
     def power_spectrum(self, cells, f_lo=None, f_hi=None, peak=False, numpy_output: bool = True):
         """What the band looks like between and around the channels (rcfm_tuner_power_spectrum; no reference
@@ -561,6 +616,8 @@ class Tuner(Injector):
     def _sync_lane(self, base):
         if self._squelch is not base._squelch:             # the base's squelch setting (a new object per set_squelch)
             self._squelch, self._squelch_dev, self._open = base._squelch, None, None
+        if self._fine is not base._fine:                   # ... and its fine-tune (a new object per retune): the next load applies it
+            self._fine, self._abi_arrays = base._fine, None
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
                 self._input_bandwidth == base._input_bandwidth:
             return
