@@ -296,13 +296,20 @@ __device__ __forceinline__ void dif_stage(float2* tile, const float2* tw, int L,
 }
 
 // W_n^e = coarse[e >> fb] * cis(-2 pi (e & mask) / n); the fine angle is < 0.03 rad.
-__device__ __forceinline__ float2 big_twiddle(const FftPassDev& d, unsigned e) {
-    const float2 c = d.coarse[e >> d.fine_bits];
+// The table lookup ("seed") on its own, for kernels that issue it with their tile's loads: inside a last stage it is a
+// dependent memory round trip in front of the first store.  big_twiddle(d, e) == big_twiddle(d, e, big_twiddle_seed(d, e)).
+__device__ __forceinline__ float2 big_twiddle_seed(const FftPassDev& d, unsigned e) {
+    return d.coarse[e >> d.fine_bits];
+}
+__device__ __forceinline__ float2 big_twiddle(const FftPassDev& d, unsigned e, float2 c) {
     const float th = d.fine_step * (float)(e & ((1u << d.fine_bits) - 1u));
     const float t2 = th * th;
     const float s = th * (1.f - t2 * (1.f / 6.f) * (1.f - t2 * (1.f / 20.f)));
     const float co = 1.f - t2 * 0.5f * (1.f - t2 * (1.f / 12.f) * (1.f - t2 * (1.f / 30.f)));
     return cmul(c, make_float2(co, -s));
+}
+__device__ __forceinline__ float2 big_twiddle(const FftPassDev& d, unsigned e) {
+    return big_twiddle(d, e, big_twiddle_seed(d, e));
 }
 
 struct LineId {
@@ -1291,17 +1298,29 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
 //
 // WinOp contract: float weight(id, l, k0) (issued with the tile's loads), void dc_bin(id, float2 v0) receives
 // the weighted bin kappa = 0.
-template <int L, int R0, int R1, int R2, int R3, int L2, int Q0, int Q1, int T, class LoadOp, class WinOp, class StoreOp>
+//
+// Decimation in registers (REG): with two stages in transform 1 its last stage leaves outputs k = g + (L / RL) q in
+// thread (g, lane); when L2 = 4 L / RL the survivors are q = 0, 1, RL - 2, RL - 1: rows l = g + (L2 / 4) q' of the short
+// spectrum, exactly the four inputs of butterfly g of a radix-4 first stage (L2 = 4 ...).  The positive Nyquist row
+// (q = 2, g = 0) and the DC bin sit in thread g = 0 as well, so weight, merge, dc_bin, swap, the radix-4 butterfly and
+// its stage twiddle (W_L2^(q' g) = W_L^((L / L2) q' g): transform 1's table, still in LDS) all run from registers: one
+// LDS write behind the "every slot has been read" barrier instead of a write, a weighting sweep and a first stage.
+template <int L, int R0, int R1, int R2, int R3, int L2, int Q0, int Q1, int Q2, int T, class LoadOp, class WinOp, class StoreOp>
 __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_decim(FftPassDev d1, FftPassDev d2, LoadOp load,
                                                                            WinOp win, StoreOp store) {
     constexpr int S = (R0 > 1) + (R1 > 1) + (R2 > 1) + (R3 > 1);
     static_assert(S >= 2 && R0 * R1 * R2 * R3 == L, "bad radix list");
-    static_assert(Q0 * Q1 == L2 && L2 % 2 == 0 && L2 < L, "bad short transform");
+    constexpr int S2 = (Q0 > 1) + (Q1 > 1) + (Q2 > 1);
+    static_assert(S2 >= 2 && Q0 * Q1 * Q2 == L2 && L2 % 2 == 0 && L2 < L, "bad short transform");
     constexpr int RL = (S == 2) ? R1 : (S == 3) ? R2 : R3;
+    constexpr int QL = (S2 == 2) ? Q1 : Q2;
     constexpr int RG = T / W;
     constexpr int nld = (L * W + T - 1) / T;
     constexpr int rowsL = L / RL, nitL = (rowsL + RG - 1) / RG;
-    constexpr int nwin = (L2 * W + T - 1) / T;          // weighting sweep: points per thread
+    constexpr int rows2 = L2 / QL;
+    static_assert(rows2 <= RG, "short transform: one sweep");
+    constexpr bool REG = S == 2 && nitL == 1 && Q0 == 4 && L2 == 4 * rowsL && RL >= 5 && L % L2 == 0;
+    constexpr int nwin = REG ? 4 : (L2 * W + T - 1) / T;   // weights per thread: its four rows / the weighting sweep's points
     __shared__ __attribute__((aligned(16))) float2 tile[L * kRowsPitch];
     __shared__ __attribute__((aligned(16))) float2 tw[L];
     const FftPass& p1 = d1.p;
@@ -1333,12 +1352,30 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
         v[it] = load.fetch(id, l, in_base, (unsigned)wcl * in_i + (unsigned)l);
     }
     float wgt[nwin];
+    if constexpr (REG) {
+        const int g = rg < rowsL ? rg : 0;
 #pragma unroll
-    for (int it = 0; it < nwin; ++it) {
-        int e = tid + T * it;
-        if ((L2 * W) % T != 0) e = e < L2 * W ? e : 0;
-        const int wl = e & (W - 1);
-        wgt[it] = win.weight(id, e >> kLogW, i0 + (wl < wvalid ? wl : 0));
+        for (int q = 0; q < 4; ++q) wgt[q] = win.weight(id, g + rowsL * q, i0 + (w < wvalid ? w : 0));
+    } else {
+#pragma unroll
+        for (int it = 0; it < nwin; ++it) {
+            int e = tid + T * it;
+            if ((L2 * W) % T != 0) e = e < L2 * W ? e : 0;
+            const int wl = e & (W - 1);
+            wgt[it] = win.weight(id, e >> kLogW, i0 + (wl < wvalid ? wl : 0));
+        }
+    }
+    // Seeds of the last stage's inter-pass twiddles (big_twiddle_seed): they depend on the line and the butterfly row
+    // only, so their table lookups travel with the tile's loads.
+    const unsigned f = (unsigned)((int64_t)(i0 + w) * p2.tw_i);
+    const int kb2 = last_stage_base<L2, Q0, Q1, QL, S2>(rg < rows2 ? rg : 0);
+    const float2 seedD = big_twiddle_seed(d2, f * (unsigned)rows2);
+    const float2 seedT = big_twiddle_seed(d2, f * (unsigned)kb2);
+    // (REG with a middle stage: the short transform's stage table goes to LDS behind transform 1's, one entry per thread)
+    float2 tw2 = make_float2(0.f, 0.f);
+    if constexpr (REG && S2 == 3) {
+        static_assert(L2 <= T, "short stage table: one entry per thread");
+        tw2 = d2.stage_tw[tid < L2 ? tid : 0];
     }
     for (int e = tid; e < L; e += T) tw[e] = d1.stage_tw[e];
 #pragma unroll
@@ -1372,73 +1409,108 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
             dft_p<RL>(&xr[it * RL]);
         }
     }
-    lds_barrier();   // every slot has been read
+    if constexpr (REG) {
+        // ---- decimation, weights, Nyquist merge, swap and transform 2's radix-4 first stage, all in registers -----
+        float2 y[4];
+        if (rg < rowsL) {
+            y[0] = xr[dft_slot<RL>(0)];
+            y[1] = xr[dft_slot<RL>(1)];
+            y[2] = xr[dft_slot<RL>(RL - 2)];      // k = L - L2 / 2 + g: row L2 / 2 + g (g = 0: the negative Nyquist row)
+            y[3] = xr[dft_slot<RL>(RL - 1)];
+            const bool first = rg == 0 && i0 + w == 0;   // bins kappa = 0 and A / 2: one lane of one tile
+            if (first) y[2] = cadd(y[2], xr[dft_slot<RL>(2)]);   // Y[A/2] = X[A/2] + X[-A/2]
 #pragma unroll
-    for (int it = 0; it < nitL; ++it) {
-        const int g = rg + RG * it;
-        if ((rowsL % RG == 0) || g < rowsL) {
-            const int kb = last_stage_base<L, R0, R1, RL, S>(g);
-#pragma unroll
-            for (int q = 0; q < RL; ++q) {
-                // kb < L / RL: the rows k = kb + (L / RL) q of this q lie in [(L/RL) q, (L/RL)(q + 1)); when that range
-                // misses both kept bands and the Nyquist row, nothing of it survives the decimation -- decided at
-                // compile time (q is unrolled), so the select, the LDS write and the butterfly's unused outputs go
-                if ((L / RL) * q > L2 / 2 && (L / RL) * (q + 1) <= L - L2 / 2) continue;
-                const int k = kb + (L / RL) * q;
-                // row of the short spectrum: positive frequencies, negative frequencies, the negative
-                // Nyquist row (kept by every line), the positive one (parked in row L2: only bin A/2 of
-                // line k_0 = 0 needs it)
-                int l = -1;
-                if (k < L2 / 2) l = k;
-                else if (k >= L - L2 / 2) l = k - (L - L2);
-                else if (k == L2 / 2) l = L2;
-                if (l >= 0) tile[lds_slot<true>(l, w)] = xr[it * RL + dft_slot<RL>(q)];
-            }
-        }
-    }
-    for (int e = tid; e < L2; e += T) tw[e] = d2.stage_tw[e];   // (every read of transform 1's table is done)
-    lds_barrier();
-
-    // ---- weights, Nyquist merge, swap for the inverse transform ----------------------------------
-#pragma unroll
-    for (int it = 0; it < nwin; ++it) {
-        const int e = tid + T * it;
-        if ((L2 * W) % T == 0 || e < L2 * W) {
-            const int l = e >> kLogW, wl = e & (W - 1);
-            float2 x = tile[lds_slot<true>(l, wl)];
-            if (l == L2 / 2 && i0 + wl == 0) {   // Y[A/2] = X[A/2] + X[-A/2] (one point of one tile)
-                const float2 y = tile[lds_slot<true>(L2, wl)];
-                x = make_float2(x.x + y.x, x.y + y.y);
-            }
-            x = make_float2(x.x * wgt[it], x.y * wgt[it]);
-            if (l == 0 && i0 + wl == 0) {
+            for (int q = 0; q < 4; ++q) y[q] = make_float2(y[q].x * wgt[q], y[q].y * wgt[q]);
+            if (first) {
                 id.i = 0;
-                win.dc_bin(id, x);
+                win.dc_bin(id, y[0]);
             }
-            tile[lds_slot<true>(l, wl)] = make_float2(x.y, x.x);
-        }
-    }
-    lds_barrier();
-
-    // ---- transform 2: a strided pass of the short plan whose input sits in LDS ---------------------
-    stage_lds<L2, Q0, L2, true, RG>(tile, tw, w, rg);
-    lds_barrier();
-    constexpr int rows2 = L2 / Q1;
-    static_assert(rows2 <= RG, "short transform: one sweep");
-    id.i = i0 + w;
-    const unsigned f = (unsigned)((int64_t)(i0 + w) * p2.tw_i);
-    if (rg < rows2) {
-        float2 x[Q1];
 #pragma unroll
-        for (int q = 0; q < Q1; ++q) x[q] = tile[lds_slot<true>(rg * Q1 + q, w)];
-        dft_p<Q1>(x);
-        const float2 D = big_twiddle(d2, f * (unsigned)(L2 / Q1));
-        float2 Tw = big_twiddle(d2, f * (unsigned)rg);
+            for (int q = 0; q < 4; ++q) y[q] = make_float2(y[q].y, y[q].x);
+            dft4(y[0], y[1], y[2], y[3]);
+#pragma unroll
+            for (int q = 1; q < 4; ++q) y[q] = cmul(y[q], tw[(L / L2) * q * rg]);
+        }
+        lds_barrier();   // every slot has been read
+        if (rg < rowsL) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) tile[lds_slot<true>(rg + rowsL * q, w)] = y[q];
+        }
+        if constexpr (S2 == 3) {
+            if (tid < L2) tw[tid] = tw2;   // (every read of transform 1's table is done)
+        }
+        lds_barrier();
+    } else {
+        lds_barrier();   // every slot has been read
+#pragma unroll
+        for (int it = 0; it < nitL; ++it) {
+            const int g = rg + RG * it;
+            if ((rowsL % RG == 0) || g < rowsL) {
+                const int kb = last_stage_base<L, R0, R1, RL, S>(g);
+#pragma unroll
+                for (int q = 0; q < RL; ++q) {
+                    // kb < L / RL: the rows k = kb + (L / RL) q of this q lie in [(L/RL) q, (L/RL)(q + 1)); when that
+                    // range misses both kept bands and the Nyquist row, nothing of it survives the decimation -- decided
+                    // at compile time (q is unrolled), so the select, the LDS write and the butterfly's unused outputs go
+                    if ((L / RL) * q > L2 / 2 && (L / RL) * (q + 1) <= L - L2 / 2) continue;
+                    const int k = kb + (L / RL) * q;
+                    // row of the short spectrum: positive frequencies, negative frequencies, the negative
+                    // Nyquist row (kept by every line), the positive one (parked in row L2: only bin A/2 of
+                    // line k_0 = 0 needs it)
+                    int l = -1;
+                    if (k < L2 / 2) l = k;
+                    else if (k >= L - L2 / 2) l = k - (L - L2);
+                    else if (k == L2 / 2) l = L2;
+                    if (l >= 0) tile[lds_slot<true>(l, w)] = xr[it * RL + dft_slot<RL>(q)];
+                }
+            }
+        }
+        for (int e = tid; e < L2; e += T) tw[e] = d2.stage_tw[e];   // (every read of transform 1's table is done)
+        lds_barrier();
+
+        // ---- weights, Nyquist merge, swap for the inverse transform ----------------------------------
+#pragma unroll
+        for (int it = 0; it < nwin; ++it) {
+            const int e = tid + T * it;
+            if ((L2 * W) % T == 0 || e < L2 * W) {
+                const int l = e >> kLogW, wl = e & (W - 1);
+                float2 x = tile[lds_slot<true>(l, wl)];
+                if (l == L2 / 2 && i0 + wl == 0) {   // Y[A/2] = X[A/2] + X[-A/2] (one point of one tile)
+                    const float2 y = tile[lds_slot<true>(L2, wl)];
+                    x = make_float2(x.x + y.x, x.y + y.y);
+                }
+                x = make_float2(x.x * wgt[it], x.y * wgt[it]);
+                if (l == 0 && i0 + wl == 0) {
+                    id.i = 0;
+                    win.dc_bin(id, x);
+                }
+                tile[lds_slot<true>(l, wl)] = make_float2(x.y, x.x);
+            }
+        }
+        lds_barrier();
+
+        // ---- transform 2: a strided pass of the short plan whose input sits in LDS ---------------------
+        stage_lds<L2, Q0, L2, true, RG>(tile, tw, w, rg);
+        lds_barrier();
+    }
+    if constexpr (S2 == 3) {
+        stage_lds<L2, Q1, L2 / Q0, true, RG>(tile, tw, w, rg);
+        lds_barrier();
+    }
+    // ---- last stage of transform 2: LDS -> registers -> memory (inter-pass twiddles from the prefetched seeds) ----
+    id.i = i0 + w;
+    if (rg < rows2) {
+        float2 x[QL];
+#pragma unroll
+        for (int q = 0; q < QL; ++q) x[q] = tile[lds_slot<true>(rg * QL + q, w)];
+        dft_p<QL>(x);
+        const float2 D = big_twiddle(d2, f * (unsigned)rows2, seedD);
+        float2 Tw = big_twiddle(d2, f * (unsigned)kb2, seedT);
         if (w < wvalid) {
 #pragma unroll
-            for (int q = 0; q < Q1; ++q) {
-                const int k = rg + (L2 / Q1) * q;
-                const float2 y = cmul(x[dft_slot<Q1>(q)], Tw);
+            for (int q = 0; q < QL; ++q) {
+                const int k = kb2 + rows2 * q;
+                const float2 y = cmul(x[dft_slot<QL>(q)], Tw);
                 Tw = cmul(Tw, D);
                 store(id, k, out_base, (unsigned)k * out_k + (unsigned)w, y);
             }
@@ -1654,15 +1726,23 @@ inline bool fft_tile2_applies(const FftPassDev& d1, const FftPassDev& d2, int ba
 
 // Spectral decimation between two transforms (k_fft_tile2_decim): (long last-pass length, short
 // first-pass length) pairs with an instantiation.
-#define RCFM_FFT_DECIM_500(X) X(500, 25, 20, 1, 1, 100, 10, 10)
-#define RCFM_FFT_DECIM_125(X) X(125, 5, 5, 5, 1, 80, 10, 8)
+// 500 -> 100 runs the short transform as 4 x 5 x 5: the radix-4 first stage is the register form of the decimation
+// (k_fft_tile2_decim, REG), then one LDS stage and a last stage on 320 of the 512 threads.  4, 25, 1 (one LDS round trip
+// and one barrier fewer, but a serial radix-25 last stage on 64 threads) measured the same per kernel and less steady per
+// step (docs/EXPERIMENTS.md, "decimation in registers").
+#ifndef RCFM_DECIM_100
+#define RCFM_DECIM_100 4, 5, 5
+#endif
+#define RCFM_FFT_DECIM_X_(X, ...) X(__VA_ARGS__)
+#define RCFM_FFT_DECIM_500(X) RCFM_FFT_DECIM_X_(X, 500, 25, 20, 1, 1, 100, RCFM_DECIM_100)
+#define RCFM_FFT_DECIM_125(X) X(125, 5, 5, 5, 1, 80, 10, 8, 1)
 #define RCFM_FFT_DECIM_PAIRS(X)          \
     RCFM_FFT_DECIM_500(X)                \
     RCFM_FFT_DECIM_125(X)
 
 inline bool fft_tile2_decim_applies(const FftPassDev& d1, const FftPassDev& d2, int batch) {
     bool fast = false;
-#define RCFM_CASE(LEN, A, B, C, D, LEN2, E, F) fast = fast || (d1.p.L == LEN && d2.p.L == LEN2);
+#define RCFM_CASE(LEN, A, B, C, D, LEN2, E, F, G) fast = fast || (d1.p.L == LEN && d2.p.L == LEN2);
     RCFM_FFT_DECIM_PAIRS(RCFM_CASE)
 #undef RCFM_CASE
     return fast && d1.p.load_along_l && !d2.p.load_along_l &&
@@ -1676,9 +1756,9 @@ inline bool launch_fft_tile2_decim(const FftPassDev& d1, const FftPassDev& d2, i
     if (!fft_tile2_decim_applies(d1, d2, batch)) return false;
     const dim3 grid((unsigned)((d1.p.n_inner + W - 1) / W), 1, (unsigned)batch);
     bool done = false;
-#define RCFM_CASE(LEN, A, B, C, D, LEN2, E, F)                                                                   \
+#define RCFM_CASE(LEN, A, B, C, D, LEN2, E, F, G)                                                                \
     if (!done && d1.p.L == LEN && d2.p.L == LEN2) {                                                             \
-        hipLaunchKernelGGL((k_fft_tile2_decim<LEN, A, B, C, D, LEN2, E, F, tile_threads(LEN), LoadOp, WinOp, StoreOp>), \
+        hipLaunchKernelGGL((k_fft_tile2_decim<LEN, A, B, C, D, LEN2, E, F, G, tile_threads(LEN), LoadOp, WinOp, StoreOp>), \
                            grid, dim3(tile_threads(LEN)), 0, s, d1, d2, ld, win, st);                           \
         done = true;                                                                                            \
     }

@@ -17,6 +17,19 @@ if [ -n "$db" ]; then
     echo "Every kernel of the traced process (input synthesis included):" >> "$root/gpurun_out/${tag}_kernel_stats.md"
     echo >> "$root/gpurun_out/${tag}_kernel_stats.md"
     python "$root/tools/rocpd_summary.py" "$db" 40 >> "$root/gpurun_out/${tag}_kernel_stats.md"
+    # launch-to-launch spread of one kernel (SPREAD_OF=<substring of its name>): sizes the margin of a per-kernel comparison
+    if [ -n "$SPREAD_OF" ]; then
+        {
+            echo
+            echo "Per-launch durations of \`$SPREAD_OF\`:"
+            echo
+            python "$root/tools/rocpd_summary.py" "$db" --launches "$SPREAD_OF"
+            echo
+            echo "... without the first three launches (2 warm-up steps + 1 profile pass):"
+            echo
+            python "$root/tools/rocpd_summary.py" "$db" --launches "$SPREAD_OF" 3
+        } >> "${out}_kernel_stats.md"
+    fi
 else
     csv=$(find "$out" -name '*kernel_stats.csv' | head -1)
     cp "$csv" "$root/gpurun_out/${tag}_kernel_stats.csv"

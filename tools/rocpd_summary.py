@@ -38,7 +38,30 @@ def main(path, limit=40, only=None):
         print("| `%s` | %d | %.3f | %.2f | %.2f |" % (short, calls, total / 1e3, avg, pct))
 
 
+def launches(path, pattern, skip=0):
+    """Per-launch durations of every kernel whose name contains `pattern` (without each kernel's first `skip` launches --
+    warm-up): what a margin on a per-launch time is sized by."""
+    db = sqlite3.connect(path)
+    q = ("select S.display_name, (K.end - K.start) / 1000.0 from rocpd_kernel_dispatch K inner join rocpd_info_kernel_symbol S "
+         "on S.id = K.kernel_id and S.guid = K.guid order by K.start")
+    by = {}
+    for name, us in db.execute(q):
+        if pattern in name:
+            by.setdefault(name, []).append(us)
+    print("| kernel | launches | min us | median us | mean us | max us | spread (max - min) us |")
+    print("|---|---:|---:|---:|---:|---:|---:|")
+    for name, v in by.items():
+        short = name.replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "").replace("rcfm::fftk::", "").replace("rcfm::", "")
+        if len(short) > 100:
+            short = short[:97] + "..."
+        s = sorted(v[skip:])
+        print("| `%s` | %d | %.2f | %.2f | %.2f | %.2f | %.2f |" % (short, len(s), s[0], s[len(s) // 2], sum(s) / len(s), s[-1], s[-1] - s[0]))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 3 and sys.argv[2] == "--launches":
+        launches(sys.argv[1], sys.argv[3], int(sys.argv[4]) if len(sys.argv) > 4 else 0)
+        sys.exit(0)
     if len(sys.argv) > 3 and sys.argv[2] == "--per-step":
         per_step(sys.argv[1], int(sys.argv[3]))
         sys.exit(0)
