@@ -44,7 +44,8 @@ extern "C" {
                             demodulator kinds RCFM_AM, RCFM_USB, RCFM_LSB (no new entry points);
                             rcfm_tuner_levels and rcfm_squelch added (new symbols only, nothing existing changed);
                             rcfm_tuner_power_spectrum added (a new symbol only, nothing existing changed);
-                            rcfm_tuner_carriers and rcfm_tuner_retune added (new symbols only, nothing existing changed) */
+                            rcfm_tuner_carriers and rcfm_tuner_retune added (new symbols only, nothing existing changed);
+                            rcfm_subcarrier_* and rcfm_pipeline_subcarrier added (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -79,6 +80,7 @@ typedef enum rcfm_demod_kind {
 
 typedef struct rcfm_tuner_s* rcfm_tuner_t;
 typedef struct rcfm_demod_s* rcfm_demod_t;
+typedef struct rcfm_subcarrier_s* rcfm_subcarrier_t;
 typedef struct rcfm_resampler_s* rcfm_resampler_t;
 typedef struct rcfm_feeder_s* rcfm_feeder_t;
 typedef struct rcfm_comm_s* rcfm_comm_t;
@@ -288,6 +290,52 @@ int rcfm_demod_destroy(rcfm_demod_t d);
  * channels [first, first+count), chunk by chunk.  audio: [count][A][ch]. */
 int rcfm_pipeline_run(rcfm_tuner_t t, rcfm_demod_t d, int first, int count, void* audio,
                       void* stream);
+
+/* ---- subcarrier tap (no reference counterpart) ------------------------------------------------------------------------
+ * What else the FM multiplex carries: RDS at 57 kHz, SCA at 67 / 92 kHz, DARC at 76 kHz, the CTCSS tone of narrow FM.  For
+ * every channel of a range, the complex baseband of the multiplex around a subcarrier frequency f, low-pass filtered and
+ * decimated to a rate a host can handle; phase loop, bit timing and decoding stay on the host (radiocore.tools.rds).
+ *
+ * Inputs.  For the B channel samples x[0..B) of one channel (one-second buffers, so B is also the sample rate in Hz):
+ *   f        an integer subcarrier frequency in Hz, |f| <= B/2;
+ *   R        an output length that divides B, with D = B / R;
+ *   h[0..T)  T real taps, T odd, 1 <= T <= 4095, centre c = (T-1)/2.
+ * Discriminator (the FM discriminator of fm.py:60-65).
+ *   th[n] = arg(x[n]) / pi
+ *   d[0]  = 0
+ *   d[n]  = th[n] - th[n-1], wrapped into [-1, 1]
+ *   d[n]  = 0 outside [0, B)
+ * Output, complex64 [count][R].
+ *   y[j]  = sum_{i=0}^{T-1} h[i] d[jD + i - c] exp(-2 pi i ((jD + i - c) f mod B) / B),   j = 0 .. R-1
+ * In words: mix the multiplex down by f, low-pass with h, keep every D-th sample.  Edges are a linear convolution with zero
+ * extension, not circular.  A subcarrier at f with frequency deviation Delta Hz and phase phi comes out as
+ * (Delta / B) sum(h) e^{i phi}.  The phase index (n f) mod B is exact integer arithmetic in 64 bits: at B = 240 000,
+ * f = 57 000 the product passes 2^32.
+ * Evaluation form.  The library evaluates
+ *   y[j]   = rot[j] sum_i g[i] d[jD + i - c]
+ *   g[i]   = h[i] exp(-2 pi i ((i-c) f mod B) / B)
+ *   rot[j] = exp(-2 pi i (jD f mod B) / B)
+ * with g and rot computed on the host in float64 and stored as complex64 tables.
+ * Determinism.  Every output's sum over i has one order, the same for every output of a handle: taps i = p, p + D, p + 2D, ...
+ * for p = 0, 1, .. in turn, a function of T and D alone (where no tile of the kernel fits the LDS, D of several thousand:
+ * 256 interleaved partial sums folded in a fixed tree, a function of T alone).  There are no floating-point atomics.  Results
+ * are bit-identical from run to run, from stream to stream, for a sub-range against the whole range, and for any chunk.
+ *
+ * create   RCFM_ERR_ARG before any device call for NULL pointers, C < 1, B < 2, R < 1, B % R != 0, |f| > B/2, ntaps even or
+ *          outside 1 .. 4095, a non-finite tap.  C = the most channels one call will pass; chunk as for rcfm_demod_create
+ *          (0 = 1024 channels at B = 240 000, proportionally more for narrower channels, up to 8192).  The handle owns g and
+ *          rot on the device and, for the pipeline form, one workspace of chunk B float32 (complex64 for a band whose inverse
+ *          FFT cannot leave phases): plain device memory, never taken from a bound arena.
+ * run      the from-samples form, as rcfm_demod_run is for the demodulators: iq [count][B] complex64 -> out [count][R].
+ * pipeline channels [first, first + count) of a loaded tuner, chunk by chunk: the tuner's inverse FFT leaves angle(x) / pi
+ *          in the workspace where its band can (else the samples), and the tap kernel reads that.  Readiness as for
+ *          rcfm_pipeline_run: RCFM_ERR_STATE before a load or outside the loaded / sharded / attached range, RCFM_ERR_INDEX
+ *          for a bad range (or count > C), RCFM_ERR_SIZE where a channel's bandwidth is not B.  It touches no demodulator
+ *          workspace or state. */
+int rcfm_subcarrier_create(int C, int B, int R, int64_t f, const float* taps_host, int ntaps, int chunk, rcfm_subcarrier_t* out);
+int rcfm_subcarrier_run(rcfm_subcarrier_t h, int count, const void* iq, void* out, void* stream);      /* iq [count][B] complex64 */
+int rcfm_pipeline_subcarrier(rcfm_tuner_t t, rcfm_subcarrier_t h, int first, int count, void* out, void* stream);
+int rcfm_subcarrier_destroy(rcfm_subcarrier_t h);
 
 /* ---- host ingest (the step before Tuner.load) -------------------------------- */
 

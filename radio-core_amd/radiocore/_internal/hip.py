@@ -83,6 +83,10 @@ SIGNATURES = {
     "rcfm_demod_get_option": [_vp, _i, ctypes.POINTER(_i)],
     "rcfm_demod_destroy": [_vp],
     "rcfm_pipeline_run": [_vp, _vp, _i, _i, _vp, _vp],
+    "rcfm_subcarrier_create": [_i, _i, _i, _i64, _fp, _i, _i, ctypes.POINTER(_vp)],
+    "rcfm_subcarrier_run": [_vp, _i, _vp, _vp, _vp],
+    "rcfm_pipeline_subcarrier": [_vp, _vp, _i, _i, _vp, _vp],
+    "rcfm_subcarrier_destroy": [_vp],
     "rcfm_host_register": [_vp, _sz],
     "rcfm_host_unregister": [_vp],
     "rcfm_feeder_create": [_sz, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp)],

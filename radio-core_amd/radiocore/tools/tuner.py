@@ -73,6 +73,7 @@ class Tuner(Injector):
         self._open = None          # device uint8 masks of the last run_all / run_each, one per launch group
         self._fine = None          # retune: None or int64 [len(channels())] bins each channel was moved up (a new object per retune)
         self._handle_fine = None   # the _fine the device handle's rolls were last set from
+        self._taps = {}            # (B, R, f, taps) -> (channels it holds, batched subcarrier handle) of subcarrier()
 
     @property
     def input_frequency(self) -> float:
@@ -349,6 +350,34 @@ class Tuner(Injector):
     def fine_tune(self):
         """int64 [len(channels())]: the bins every channel has been moved up by ``retune`` since the channel list last changed."""
         return np.zeros(len(self._bounds), np.int64) if self._fine is None else self._fine.copy()
+
+    # ---- subcarrier tap (rcfm_pipeline_subcarrier; no reference counterpart) ---------------------------------------------
+
+    def subcarrier(self, tap, first: int = 0, count: int = None, numpy_output: bool = True):
+        """What else the FM multiplex of every channel carries: complex64 [count, tap.output_size], the baseband around the
+        subcarrier of ``tap`` (a ``radiocore.analog.Subcarrier``: frequency, low-pass, output rate) for channels
+        [first, first + count) of the loaded buffer (count None: up to the last channel), which must all have the tap's
+        input size as bandwidth.  Valid after ``load`` / ``adopt``, on the current stream; it runs the channels' inverse
+        FFT once more and touches no demodulator state, so it may come before or after ``run_all``.  RDS:
+        ``radiocore.tools.rds`` decodes the 57 kHz tap on the host."""
+        handle = self._ready()
+        first = int(first)
+        if count is None:                   # the rest of the tuner's channels, or of the shard's after ``shard``
+            _, lo, n = self._launch_plan()
+            first = max(first, lo)
+            count = max(lo + n - first, 0)
+        count = int(count)
+        if first < 0 or count < 0 or first + count > len(self._bounds):
+            raise IndexError("list index out of range")
+        # one batched handle per (B, R, f, taps), sized for all channels like _batched_demod's: a longer channel list gets
+        # a new one, the old one goes
+        key = tap._key()
+        held = self._taps.get(key)
+        if held is None or held[0] < len(self._bounds):
+            self._taps[key] = held = (len(self._bounds), tap._create(len(self._bounds), 0))
+        out = hip.empty((count, tap._output_size), self._torch.complex64)
+        hip.check(self._lib.rcfm_pipeline_subcarrier(handle, held[1].value, first, count, hip.ptr(out), hip.stream()))
+        return self._result(out, self._cuda and not numpy_output)
 
     def power_spectrum(self, cells, f_lo=None, f_hi=None, peak=False, numpy_output: bool = True):
         """What the band looks like between and around the channels (rcfm_tuner_power_spectrum; no reference

@@ -1,0 +1,246 @@
+"""GPU: the subcarrier tap (rcfm_subcarrier_*, rcfm_pipeline_subcarrier; radiocore.Subcarrier, Tuner.subcarrier) against
+its definition in include/rcfm.h, evaluated in float64 by tests/subcarrier_model.py on the same complex64 input.
+
+Bounds: max|delta| / max|truth| per channel, worst channel, within primitives_model.gpu_bound(yardstick) = min(4 x yardstick,
+1e-4), the yardstick being the float32 CPU figure of the very case that tests/test_subcarrier_model.py pins.  Every case
+prints its worst row and its bound.  Sub-ranges, streams and chunk sizes are compared bit for bit.
+"""
+
+import ctypes
+
+import numpy as np
+import pytest
+
+import primitives_model as pm
+import rds_model
+import subcarrier_model as sm
+from conftest import ROOT, have_gpu
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not have_gpu(), reason="needs an MI355X")]
+
+ERR_SIZE, ERR_INDEX, ERR_STATE = -1, -2, -5
+
+
+@pytest.fixture(scope="module")
+def rc():
+    import radiocore
+    assert radiocore.HasCuda(), "librcfm.so did not load or sees no device"
+    return radiocore
+
+
+@pytest.fixture(scope="module")
+def hip(rc):
+    from radiocore._internal import hip
+    return hip
+
+
+def _truth(case):
+    B, R, f, T = case
+    if case not in _truth.cache:
+        _truth.cache[case] = sm.truth(sm.case_input(B), R, f, sm.taps(T))
+    return _truth.cache[case]
+
+
+_truth.cache = {}
+
+
+# ---- the standalone cases ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("batch", (1, 3))
+@pytest.mark.parametrize("case", list(sm.CASES), ids=lambda c: "B%d-R%d-f%d-T%d" % c)
+def test_case_within_its_bound(rc, case, batch):
+    B, R, f, T = case
+    x = sm.case_input(B)[:batch]
+    tap = rc.Subcarrier(B, R, f, sm.taps(T), batch=batch)
+    y = tap.run(x[0] if batch == 1 else x)
+    assert y.dtype == np.complex64 and y.shape == ((R,) if batch == 1 else (batch, R))
+    err = pm.row_errors(y.reshape(batch, R), _truth(case)[:batch])
+    bound = pm.gpu_bound(sm.CASES[case])
+    print("B = %d, R = %d, f = %d, T = %d, batch %d: worst row %d at %.3g, bound %.3g"
+          % (B, R, f, T, batch, int(np.argmax(err)), float(np.max(err)), bound))
+    assert np.max(err) <= bound
+
+
+def _raw_run(hip, handle, x_dev, count, R, stream=None):
+    import torch
+    y = torch.full((count, R), float("nan"), dtype=torch.complex64, device="cuda")
+    hip.check(hip.lib().rcfm_subcarrier_run(handle.value, count, hip.ptr(x_dev), hip.ptr(y),
+                                            stream if stream is not None else hip.stream()))
+    torch.cuda.synchronize()
+    return y.cpu().numpy()
+
+
+@pytest.mark.parametrize("case", [(240000, 9600, 57000, 241), (1001, 91, 77, 15), (6000, 240, 2999, 257), (6000, 1, 1234, 4095)],
+                         ids=lambda c: "B%d-R%d-f%d-T%d" % c)
+def test_sub_range_stream_and_chunk_are_bit_identical(rc, hip, case):
+    import torch
+    B, R, f, T = case
+    x = hip.to_device(sm.case_input(B).copy())
+    whole = rc.Subcarrier(B, R, f, sm.taps(T), batch=3)
+    y = _raw_run(hip, whole._handle, x, 3, R)
+    assert not np.any(np.isnan(y.real))
+    # rows 1 - 2 alone, count = 2
+    alone = _raw_run(hip, whole._handle, x[1:], 2, R)
+    assert np.array_equal(alone.view(np.uint32), y[1:].view(np.uint32))
+    # a second stream
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    again = _raw_run(hip, whole._handle, x, 3, R, ctypes.c_void_p(side.cuda_stream))
+    assert np.array_equal(again.view(np.uint32), y.view(np.uint32))
+    # one channel per launch
+    single = rc.Subcarrier(B, R, f, sm.taps(T), batch=3, chunk=1)
+    assert np.array_equal(_raw_run(hip, single._handle, x, 3, R).view(np.uint32), y.view(np.uint32))
+    # more channels than the handle was created for
+    assert hip.lib().rcfm_subcarrier_run(single._handle.value, 4, hip.ptr(x), hip.ptr(x), hip.stream()) == ERR_INDEX
+
+
+def test_constructor_refuses_what_the_library_would(rc):
+    for kw in (dict(taps=np.ones(4)), dict(output_size=7), dict(frequency=501), dict(frequency=10.5), dict(taps=[1.0, np.inf, 1.0]),
+               dict(batch=0), dict(taps=np.ones(4097))):
+        args = dict(input_size=1000, output_size=100, frequency=10, taps=np.ones(3))
+        args.update(kw)
+        with pytest.raises(ValueError):
+            rc.Subcarrier(**args)
+    tap = rc.Subcarrier(1000, 100, 10, np.ones(3))
+    with pytest.raises(ValueError, match="mismatch"):
+        tap.run(np.zeros(999, np.complex64))
+
+
+# ---- through the Tuner ----------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def rds_tuner(rc):
+    tuner = rc.Tuner()
+    for fc in rds_model.CENTRES:
+        tuner.add_channel(fc, rds_model.B, rc.WBFM(rds_model.B, 48000))
+    tuner.request_bandwidth(float(rds_model.N))
+    assert tuner.input_frequency == rds_model.input_frequency()
+    R, f, T, cutoff = sm.RDS_TAP
+    from radiocore.tools import rds
+    tap = rc.Subcarrier(rds_model.B, R, f, rds.taps(rds_model.B, R, T, cutoff))
+    return tuner, tap
+
+
+def test_tuner_refuses_before_a_load(rc, hip, rds_tuner):
+    tuner, tap = rds_tuner
+    fresh = rc.Tuner()
+    for fc in rds_model.CENTRES:
+        fresh.add_channel(fc, rds_model.B, rc.WBFM(rds_model.B, 48000))
+    with pytest.raises(RuntimeError):
+        fresh.subcarrier(tap)
+    handle = fresh._device_tuner(rds_model.N)
+    import torch
+    out = torch.zeros((3, sm.RDS_TAP[0]), dtype=torch.complex64, device="cuda")
+    lib = hip.lib()
+    batched = tap._create(3, 0)
+    assert lib.rcfm_pipeline_subcarrier(handle, batched.value, 0, 3, hip.ptr(out), hip.stream()) == ERR_STATE
+    assert b"rcfm_pipeline_subcarrier" in lib.rcfm_last_error()
+    assert lib.rcfm_pipeline_subcarrier(handle, batched.value, 2, 2, hip.ptr(out), hip.stream()) == ERR_INDEX
+    assert lib.rcfm_pipeline_subcarrier(handle, tap._handle.value, 0, 3, hip.ptr(out), hip.stream()) == ERR_INDEX   # a handle for one channel
+
+
+def test_rds_band_through_the_tuner(rc, rds_tuner):
+    from radiocore.tools import rds
+    tuner, tap = rds_tuner
+    R = sm.RDS_TAP[0]
+    tuner.load(rds_model.band().copy())
+    before = tuner.run_all()
+    y = tuner.subcarrier(tap)
+    tuner.reset_states()                              # (WBFM carries de-emphasis state from call to call)
+    assert np.array_equal(tuner.run_all(), before)    # the same audio before and after the tap call
+    third = tuner.run_all()                           # ... and the state goes on as if the tap had never run (below)
+    assert y.dtype == np.complex64 and y.shape == (3, R)
+    err = pm.row_errors(y, sm.rds_truth())
+    for k, (e, yard) in enumerate(zip(err, sm.RDS_YARDSTICK)):
+        print("station %d: %.3g, bound %.3g" % (k, e, pm.gpu_bound(yard)))
+    for e, yard in zip(err, sm.RDS_YARDSTICK):
+        assert e <= pm.gpu_bound(yard)
+    for k, (pi, ps) in enumerate(rds_model.STATIONS):
+        found = rds.groups(rds.bits(y[k], R))
+        print("station %d: %d groups, PI %04X, PS %r" % (k, len(found), rds.station(found)[0] or 0, rds.station(found)[1]))
+        assert len(found) >= 8 and rds.station(found) == (pi, ps)
+    # a sub-range is bit-identical to those rows of the full range, and so is a second call
+    part = tuner.subcarrier(tap, first=1, count=2)
+    assert np.array_equal(part.view(np.uint32), y[1:3].view(np.uint32))
+    assert np.array_equal(tuner.subcarrier(tap).view(np.uint32), y.view(np.uint32))
+    assert len(tuner._taps) == 1                      # one batched handle per (B, R, f, taps)
+    # a tap for another channel width
+    other = rc.Subcarrier(120000, 4800, 57000, rds.taps(120000, 4800, cutoff=2000.0))
+    with pytest.raises(ValueError, match="mismatch"):
+        tuner.subcarrier(other)
+    with pytest.raises(IndexError):
+        tuner.subcarrier(tap, first=2, count=2)
+    # the tap touches no demodulator workspace or state: a twin tuner that never runs the tap gives the same audio for
+    # the same buffer twice in a row
+    twin = rc.Tuner()
+    for fc in rds_model.CENTRES:
+        twin.add_channel(fc, rds_model.B, rc.WBFM(rds_model.B, 48000))
+    twin.request_bandwidth(float(rds_model.N))
+    twin.load(rds_model.band().copy())
+    assert np.array_equal(twin.run_all(), before)
+    assert np.array_equal(twin.run_all(), third)
+
+
+def test_band_without_phase_output(rc, hip):
+    """B = 3001 is prime: the Tuner's inverse FFT of these channels is rocFFT's, which hands over samples, not phases."""
+    n, B, R, f, T = sm.PRIME_BAND
+    plan = hip.FftPlan()
+    assert hip.lib().rcfm_fft_describe(B, 0, ctypes.byref(plan)) != 0, "the engine has a plan for this length now: pick another"
+    x, f_in, centres = sm.prime_band()
+    tuner = rc.Tuner()
+    for fc in centres:
+        tuner.add_channel(fc, B, rc.FM(B, 1001))
+    tuner.request_bandwidth(float(n))
+    assert tuner.input_frequency == f_in
+    tuner.load(x.copy())
+    tap = rc.Subcarrier(B, R, f, sm.taps(T))
+    y = tuner.subcarrier(tap)
+    want = sm.truth(sm.prime_band_channels()[0], R, f, sm.taps(T))
+    err = pm.row_errors(y, want)
+    bound = pm.gpu_bound(sm.PRIME_BAND_YARDSTICK)
+    print("prime band: worst channel %d at %.3g, bound %.3g" % (int(np.argmax(err)), float(np.max(err)), bound))
+    assert np.max(err) <= bound
+    # the from-samples form on the Tuner's own channel samples is the same kernel on the same input
+    iq = tuner.run_channels(0, 3)
+    direct = rc.Subcarrier(B, R, f, sm.taps(T), batch=3).run(iq)
+    assert np.array_equal(direct.view(np.uint32), y.view(np.uint32))
+
+
+def test_tap_follows_a_growing_channel_list(rc):
+    """A tap used before add_channel serves the longer list afterwards: the Tuner's batched handle is sized for all channels."""
+    n, B, R, f, T = sm.PRIME_BAND
+    x, f_in, centres = sm.prime_band()
+    tuner = rc.Tuner()
+    for fc in centres:
+        tuner.add_channel(fc, B, rc.FM(B, 1001))
+    tuner.request_bandwidth(float(n))
+    tuner.load(x.copy())
+    tap = rc.Subcarrier(B, R, f, sm.taps(T))
+    want = sm.truth(sm.prime_band_channels()[0], R, f, sm.taps(T))
+    bound = pm.gpu_bound(sm.PRIME_BAND_YARDSTICK)
+    assert np.max(pm.row_errors(tuner.subcarrier(tap), want)) <= bound
+    for fc in (1e6 + 6 * B, 1e6 - 6 * B):            # two empty channels, the band's centre stays where it was
+        tuner.add_channel(fc, B, rc.FM(B, 1001))
+    tuner.request_bandwidth(float(n))
+    assert tuner.input_frequency == f_in
+    tuner.load(x.copy())
+    y = tuner.subcarrier(tap)
+    assert y.shape == (5, R) and np.all(np.isfinite(y.view(np.float32)))
+    err = pm.row_errors(y[:3], want)
+    print("five channels: worst of the first three %.3g, bound %.3g" % (float(np.max(err)), bound))
+    assert np.max(err) <= bound
+    assert len(tuner._taps) == 1
+
+
+def test_fm_rds_example():
+    """examples/fm_rds.py names its three stations."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("fm_rds", os.path.join(ROOT, "examples", "fm_rds.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    audio, found = mod.run()
+    assert audio.shape == (3, mod.AUDIO, 2)
+    for (_, pi, ps), (got_pi, got_ps, groups) in zip(mod.STATIONS, found):
+        print("PI %04X PS %r (%d groups)" % (got_pi or 0, got_ps, groups))
+        assert (got_pi, got_ps) == (pi, ps) and groups >= 8
