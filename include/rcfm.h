@@ -45,7 +45,9 @@ extern "C" {
                             rcfm_tuner_levels and rcfm_squelch added (new symbols only, nothing existing changed);
                             rcfm_tuner_power_spectrum added (a new symbol only, nothing existing changed);
                             rcfm_tuner_carriers and rcfm_tuner_retune added (new symbols only, nothing existing changed);
-                            rcfm_subcarrier_* and rcfm_pipeline_subcarrier added (new symbols only, nothing existing changed) */
+                            rcfm_subcarrier_* and rcfm_pipeline_subcarrier added (new symbols only, nothing existing changed);
+                            rcfm_agc, rcfm_demod_set_agc and rcfm_demod_get / set_agc_state added (new symbols only; a handle
+                            that never calls rcfm_demod_set_agc launches what it launched before) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -285,6 +287,48 @@ enum { RCFM_OPT_NARROW_TILES = 4, RCFM_OPT_STATE_FENCE = 5, RCFM_OPT_GRAPH = 10 
 int rcfm_demod_set_option(rcfm_demod_t d, int option, int value);
 int rcfm_demod_destroy(rcfm_demod_t d);
 
+/* ---- stateful AGC for AM and SSB (no reference counterpart) ----------------------------------------------------------
+ * RCFM_AM, RCFM_USB and RCFM_LSB normalise every buffer by a statistic of that buffer alone (the carrier mean, the RMS):
+ * the gain steps at every buffer boundary, and a speaker who pauses comes out louder in that buffer than in its neighbours.
+ * An AGC replaces that statistic by a follower whose value is carried from buffer to buffer.
+ *
+ * Definition.  A row is v[0..n), float32, at audio rate.  Parameters: decay_samples > 0, with
+ * lambda = exp(-1 / decay_samples) and alpha = 1 - lambda (both formed in float64); level > 0; floor >= 0; all finite; and
+ * one float32 of state s per row.
+ *   RCFM_AGC_PEAK (USB / LSB)   e[n] = max(|v[n]|, lambda e[n-1]),           e[-1] = s
+ *                               audio[n] = clip(level v[n] / max(e[n], floor), +-0.999)
+ *   RCFM_AGC_CARRIER (AM)       c[n] = c[n-1] + alpha (v[n] - c[n-1]),       c[-1] = s
+ *                               audio[n] = clip(level (v[n] - c[n]) / max(c[n], floor), +-0.999)
+ * In both modes the output is 0 where the denominator is not > 0, and s becomes the follower's value after the last
+ * sample.  s < 0 (the reset value -1) means "no history": PEAK starts from e[-1] = 0, CARRIER from c[-1] = mean(v) of this
+ * call's row, summed in float64 in a fixed order.  floor bounds the gain at level / floor, so an empty channel does not
+ * come out at full scale.  Non-finite input may spoil its own row from that sample on, never another row.
+ * Evaluation.  PEAK never multiplies lambda in sample after sample: e[n] is the largest |v[k]| exp2(-(n - k) log2(e) /
+ * decay_samples), evaluated from that sample, the exponent in float64.  CARRIER runs its recurrence in float64 in the
+ * c + alpha (v - c) form, whose DC gain is exactly 1.  There are no atomics and the order of every operation is a function
+ * of n alone: bit-identical from run to run, from stream to stream, for a sub-range of rows against the whole range and
+ * for any chunk of a demodulator.
+ *
+ * rcfm_agc        the primitive: v [C][n] -> audio [C][n], state [C] float32 DEVICE, read and updated.  audio == v (in
+ *                 place) is allowed, any other overlap is refused.  C within the primitives' limit below.
+ *                 RCFM_ERR_ARG, before any device call: a NULL pointer, C < 1 or > 65535, n < 1, an unknown mode,
+ *                 decay_samples not finite or <= 0, level not finite or <= 0, floor not finite or < 0, partial overlap.
+ * set_agc         AM handles select CARRIER, USB / LSB handles PEAK; any other kind: RCFM_ERR_ARG.  decay_samples == 0
+ *                 switches the AGC off again (the default; level and floor are then ignored).  With AGC on, the handle
+ *                 runs the AGC tail in place of its per-buffer normalisation on every route of rcfm_demod_run and
+ *                 rcfm_pipeline_run.  The handle owns one state float per channel; set_agc (on) gives the handle a fresh
+ *                 state of its own, reset to -1, so call it before rcfm_demod_bind_state.
+ *                 rcfm_demod_reset_state resets the AGC state to -1 as well.
+ * get / set_agc_state   [C] float32, host memory; RCFM_ERR_STATE while the AGC is off.
+ * rcfm_demod_bind_state shares the AGC state the way it shares the de-emphasis state (slot `index` of `batched`), and
+ *                 requires equal AGC settings on both handles; RCFM_OPT_STATE_FENCE orders the AGC tail across streams.
+ * RCFM_OPT_GRAPH  a handle with AGC on does not capture: it keeps launching its chain, whatever the option says.
+ * Profile stages  the AGC tail is timed as the stage of the kernel it replaces (am_tail, ssb_tail). */
+enum { RCFM_AGC_PEAK = 0, RCFM_AGC_CARRIER = 1 };
+int rcfm_demod_set_agc(rcfm_demod_t d, double decay_samples, float level, float floor);
+int rcfm_demod_get_agc_state(rcfm_demod_t d, float* state_host, void* stream);
+int rcfm_demod_set_agc_state(rcfm_demod_t d, const float* state_host, void* stream);
+
 /* Whole hot path for one wideband buffer already loaded with rcfm_tuner_load:
  * the loop of examples/multi_fm_server.py:100-106 (run -> demodulator.run) for
  * channels [first, first+count), chunk by chunk.  audio: [count][A][ch]. */
@@ -398,7 +442,7 @@ int rcfm_comm_destroy(rcfm_comm_t c);
 
 /* Limits, checked on the host before anything is launched (RCFM_ERR_ARG beyond them):
  *   C      1 .. 65535 signals per call, for every entry point that takes C (rcfm_resampler_create, rcfm_filtfilt,
- *          rcfm_lfilter_fir, rcfm_hilbert, rcfm_discriminator): the signal index is a grid coordinate
+ *          rcfm_lfilter_fir, rcfm_agc, rcfm_hilbert, rcfm_discriminator): the signal index is a grid coordinate
  *   ntaps  rcfm_filtfilt 1 .. 2867, rcfm_lfilter_fir 1 .. 5461: the kernels keep the taps and a tile of the signal
  *          in 64 KiB of LDS
  *   count  rcfm_pll_phase: at most 4 294 967 040 samples (one thread each)
@@ -423,6 +467,10 @@ int rcfm_filtfilt(int C, int n, const float* taps_host, int ntaps, const void* x
  * (the final state is built from x after y is written, and a tile of y needs the inputs before it). */
 int rcfm_lfilter_fir(int C, int n, const float* taps_host, int ntaps, void* state, const void* x,
                      void* y, void* stream);
+/* The AGC tail as a primitive (definition: "stateful AGC" above): v [C][n] -> audio [C][n] float32, state [C] float32
+ * DEVICE, read and updated in place.  audio == v allowed; any partial overlap is refused. */
+int rcfm_agc(int C, int n, int mode, double decay_samples, float level, float floor, void* state, const void* v,
+             void* audio, void* stream);
 /* PLL.step, pll.py:25-34 = scipy.signal.hilbert: x [C][n] float32 -> z [C][n] complex64. */
 int rcfm_hilbert(int C, int n, const void* x, void* z, void* stream);
 /* PLL.real / PLL.image, pll.py:36-58: out = Re or Im of z^mult / |z^mult|;

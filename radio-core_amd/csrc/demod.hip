@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "agc.h"
 #include "api_internal.h"
 
 using namespace rcfm;
@@ -50,7 +51,7 @@ struct rcfm_demod_s {
     };
     size_t state_off = 0;   // floats into state_buf
     float* state_ptr() const { return state_buf->as<float>() + state_off; }
-    float* state_at(int first) const { return state_ptr() + (size_t)first * ch * 50; }   // channel `first`'s slot
+    float* state_at(int first) const { return state_ptr() + (size_t)first * state_stride(); }   // channel `first`'s slot
     float side_tap = 0.23f;
     ResampleGeom geom;   // B -> A, real, Hamming
     PlanCache r2c_B, c2c_inv_B, c2c_fwd_B, c2c_inv_A, c2r_A;
@@ -112,6 +113,21 @@ struct rcfm_demod_s {
     // MFM and WBFM carry de-emphasis state from buffer to buffer; FM, AM, USB and LSB carry none.
     bool stateful() const { return kind == RCFM_MFM || kind == RCFM_WBFM; }
     bool ssb() const { return kind == RCFM_USB || kind == RCFM_LSB; }
+
+    // rcfm_demod_set_agc (AM, USB, LSB): the AGC tail instead of the per-buffer normalisation.  Its state -- one float
+    // per channel, -1 = no history -- lives in state_buf like the de-emphasis state of MFM / WBFM, so binding and the
+    // fence treat both alike; a handle's kind decides the stride of a channel's slot.
+    bool agc_on = false;
+    double agc_decay = 0.0;
+    float agc_level = 0.f, agc_floor = 0.f;
+    bool carries_state() const { return stateful() || agc_on; }
+    size_t state_stride() const { return stateful() ? (size_t)ch * 50 : 1; }   // floats per channel
+    void agc_tail(int first, int cnt, float* audio, hipStream_t s) {
+        StateFence fence(*this, s);
+        StageTimer tm(kind == RCFM_AM ? ST_AM_TAIL : ST_SSB_TAIL, s);
+        launch_agc_tail(kind == RCFM_AM ? RCFM_AGC_CARRIER : RCFM_AGC_PEAK, audio, audio, A, cnt,
+                        agc_params(agc_decay, agc_level, agc_floor), state_at(first), s);
+    }
 
     void alloc() {
         const size_t c = (size_t)chunk;
@@ -198,6 +214,11 @@ struct rcfm_demod_s {
     }
 
     void reset_state(hipStream_t s) {
+        if (agc_on) {
+            const std::vector<float> all((size_t)C, -1.f);
+            RC_HIP(hipMemcpyAsync(state_ptr(), all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice, s));
+            RC_HIP(hipStreamSynchronize(s));
+        }
         if (!stateful()) return;
         std::vector<float> all((size_t)C * ch * 50);
         for (size_t i = 0; i < all.size(); ++i) all[i] = zi_h[i % 50];
@@ -304,11 +325,11 @@ struct rcfm_demod_s {
             return;
         }
         if (kind == RCFM_AM) {
-            run_am(cnt, iq, audio, s, false);
+            run_am(first, cnt, iq, audio, s, false);
             return;
         }
         if (ssb()) {
-            run_ssb(cnt, iq, audio, s);
+            run_ssb(first, cnt, iq, audio, s);
             return;
         }
         // fm.py:60-66  discriminator, then Decimate(B -> A) into the audio (FM) or into v, which mfm.py:63-65 de-emphasises
@@ -340,12 +361,16 @@ struct rcfm_demod_s {
     // AM (include/rcfm.h, RCFM_AM): envelope |x| into buf_m -- unless the tuner's last pass already stored it there
     // (envelope_ready, rcfm_pipeline_run) --, FM's real-signal routes straight into the audio, then the carrier
     // normalisation in place.  Its mean comes from the DC bin when the route left one.
-    void run_am(int cnt, const float2* iq, float* audio, hipStream_t s, bool envelope_ready) {
+    void run_am(int first, int cnt, const float2* iq, float* audio, hipStream_t s, bool envelope_ready) {
         if (!envelope_ready) {
             StageTimer tm(ST_ENVELOPE, s);
             launch_envelope(iq, buf_m.as<float>(), (int64_t)cnt * B, s);
         }
         const bool dc = run_real(cnt, audio, s, nullptr, PhaseRows{});
+        if (agc_on) {
+            agc_tail(first, cnt, audio, s);
+            return;
+        }
         StageTimer tm(ST_AM_TAIL, s);
         launch_am_tail(audio, A, cnt, dc ? buf_dc.as<float2>() : nullptr, s);
     }
@@ -355,7 +380,11 @@ struct rcfm_demod_s {
         return SsbSource{X, base32, N, B, kind == RCFM_LSB, geom.wr.as<float>(), geom.nyq_factor};
     }
 
-    void ssb_tail(int cnt, float* audio, hipStream_t s) {
+    void ssb_tail(int first, int cnt, float* audio, hipStream_t s) {
+        if (agc_on) {
+            agc_tail(first, cnt, audio, s);
+            return;
+        }
         StageTimer tm(ST_SSB_TAIL, s);
         launch_ssb_tail(audio, A, cnt, RCFM_SSB_LEVEL, s);
     }
@@ -373,12 +402,12 @@ struct rcfm_demod_s {
             TILE_CALL(narrow_launch(*eng_A, (cnt + 1) / 2, opt_narrow), fused_ssb_ifft, *eng_A,
                       ssb_source(t.spectrum(), t.base_dev.as<int32_t>() + first, t.n), audio, buf_TA.as<float2>(), cnt, s);
         }
-        ssb_tail(cnt, audio, s);
+        ssb_tail(first, cnt, audio, s);
     }
 
     // USB / LSB, route 2, from channel samples: FFT_B keeping |k| <= min(A, B) / 2, then the same inverse transform
     // reading those spectra; lengths outside the engine take rocFFT around a select-and-weight kernel.
-    void run_ssb(int cnt, const float2* iq, float* audio, hipStream_t s) {
+    void run_ssb(int first, int cnt, const float2* iq, float* audio, hipStream_t s) {
         if (eng_B && eng_A) {
             buf_Z.reserve((size_t)chunk * B * sizeof(float2));
             buf_T.reserve((size_t)chunk * eng_B->tmp_stride() * sizeof(float2));
@@ -410,7 +439,7 @@ struct rcfm_demod_s {
             StageTimer tm(ST_IFFT_A, s);
             f2.exec(buf_V.get(), audio, work.get(), s);
         }
-        ssb_tail(cnt, audio, s);
+        ssb_tail(first, cnt, audio, s);
     }
 
     // wbfm.py:77-80  FM(B->B) and the pilot band-pass
@@ -644,7 +673,7 @@ struct rcfm_demod_s {
     // RCFM_OPT_GRAPH for a one-channel call: replay the graph captured for these pointers, or capture one on the second
     // call in a row with them.  false: the caller launches the chain itself.
     bool run_graphed(int first, const float2* iq, float* audio, hipStream_t s) {
-        if (!opt_graph || !eng_B || g_prof.mask != 0 || state_buf->armed) return false;
+        if (!opt_graph || !eng_B || g_prof.mask != 0 || state_buf->armed || agc_on) return false;   // AGC: never captured
         const float* st = stateful() ? state_ptr() : nullptr;
         for (auto& g : graphs)
             if (g.iq == iq && g.audio == audio && g.first == first && g.state == st) {
@@ -789,10 +818,14 @@ int rcfm_demod_bind_state(rcfm_demod_t single, rcfm_demod_t batched, int index, 
         RC_REQUIRE(single != batched && single->kind == batched->kind && single->A == batched->A &&
                        single->tau == batched->tau,
                    RCFM_ERR_ARG, "bind_state needs demodulators of one class, audio rate and time constant");
+        RC_REQUIRE(single->agc_on == batched->agc_on &&
+                       (!single->agc_on || (single->agc_decay == batched->agc_decay && single->agc_level == batched->agc_level &&
+                                            single->agc_floor == batched->agc_floor)),
+                   RCFM_ERR_ARG, "bind_state needs equal AGC settings on both demodulators");
         require_channels(index, single->C, batched->C);
-        if (!single->stateful()) return;   // fm.py carries no state, nor do AM, USB and LSB
-        const size_t per = (size_t)single->C * single->ch * 50;
-        const size_t slot = batched->state_off + (size_t)index * single->ch * 50;
+        if (!single->carries_state()) return;   // fm.py carries no state, nor do AM, USB and LSB without AGC
+        const size_t per = (size_t)single->C * single->state_stride();
+        const size_t slot = batched->state_off + (size_t)index * single->state_stride();
         float* dst = batched->state_at(index);
         if (single->state_buf == batched->state_buf && single->state_off == slot) return;   // already bound to this slot
         if (move_history) {
@@ -861,6 +894,49 @@ int rcfm_demod_get_option(rcfm_demod_t d, int option, int* value) {
     });
 }
 
+int rcfm_demod_set_agc(rcfm_demod_t d, double decay_samples, float level, float floor) {
+    return guarded([&] {
+        RC_REQUIRE(d, RCFM_ERR_ARG, "NULL handle");
+        RC_REQUIRE(d->kind == RCFM_AM || d->ssb(), RCFM_ERR_ARG, "AGC is for AM, USB and LSB demodulators");
+        RC_REQUIRE(std::isfinite(decay_samples) && decay_samples >= 0.0, RCFM_ERR_ARG, "AGC decay_samples must be finite and >= 0");
+        if (decay_samples == 0.0) {   // off again: the per-buffer normalisation
+            d->agc_on = false;
+            return;
+        }
+        RC_REQUIRE(std::isfinite(level) && level > 0.f, RCFM_ERR_ARG, "AGC level must be finite and > 0");
+        RC_REQUIRE(std::isfinite(floor) && floor >= 0.f, RCFM_ERR_ARG, "AGC floor must be finite and >= 0");
+        // a state of this handle's own (a fence armed on a shared one stays with the others)
+        d->state_buf = std::make_shared<rcfm_demod_s::StateBuf>();
+        d->state_buf->reset((size_t)d->C * sizeof(float));
+        d->state_off = 0;
+        d->agc_on = true;
+        d->agc_decay = decay_samples;
+        d->agc_level = level;
+        d->agc_floor = floor;
+        d->reset_state(nullptr);
+    });
+}
+
+int rcfm_demod_get_agc_state(rcfm_demod_t d, float* state_host, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(d->agc_on, RCFM_ERR_STATE, "this demodulator has no AGC (rcfm_demod_set_agc)");
+        RC_HIP(hipMemcpyAsync(state_host, d->state_ptr(), (size_t)d->C * sizeof(float), hipMemcpyDeviceToHost,
+                              as_stream(stream)));
+        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+    });
+}
+
+int rcfm_demod_set_agc_state(rcfm_demod_t d, const float* state_host, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(d->agc_on, RCFM_ERR_STATE, "this demodulator has no AGC (rcfm_demod_set_agc)");
+        RC_HIP(hipMemcpyAsync(d->state_ptr(), state_host, (size_t)d->C * sizeof(float), hipMemcpyHostToDevice,
+                              as_stream(stream)));
+        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+    });
+}
+
 int rcfm_demod_get_taps(rcfm_demod_t d, float* deemph51_host, float* pilot41_host) {
     return guarded([&] {
         RC_REQUIRE(d, RCFM_ERR_ARG, "NULL handle");
@@ -904,7 +980,7 @@ int rcfm_pipeline_run(rcfm_tuner_t t, rcfm_demod_t d, int first, int count, void
                     ArenaScope ts(t->arena);
                     t->run(c0, cnt, nullptr, s, d->buf_m.as<float>(), 0, d->opt_narrow, /*envelope=*/true);
                 }
-                d->run_am(cnt, nullptr, out_c, s, /*envelope_ready=*/true);
+                d->run_am(c0, cnt, nullptr, out_c, s, /*envelope_ready=*/true);
                 continue;
             }
             // Every demodulator starts with the FM discriminator, which only needs the samples' phases:

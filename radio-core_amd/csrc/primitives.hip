@@ -1,9 +1,11 @@
 // Single-stage entry points outside the handles' chains: the resampler, FIR filters, the analytic signal, the PLL
 // phase, the discriminator and the FFT engine / rocFFT transforms (rcfm_fft_*).
 
+#include <cmath>
 #include <cstring>
 #include <tuple>
 
+#include "agc.h"
 #include "api_internal.h"
 
 using namespace rcfm;
@@ -226,6 +228,28 @@ int rcfm_lfilter_fir(int C, int n, const float* taps_host, int ntaps, void* stat
         launch_fir(static_cast<const float*>(x), static_cast<float*>(y), n, 1, C, td->as<float>(), ntaps,
                    static_cast<const float*>(state), nullptr, s);
         launch_fir_state(static_cast<const float*>(x), n, 1, C, td->as<float>(), ntaps, static_cast<float*>(state), s);
+    });
+}
+
+int rcfm_agc(int C, int n, int mode, double decay_samples, float level, float floor, void* state, const void* v,
+             void* audio, void* stream) {
+    return guarded([&] {
+        RC_REQUIRE(state && v && audio, RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(C >= 1 && n >= 1, RCFM_ERR_ARG, "bad agc size");
+        RC_REQUIRE(C <= kMaxBatch, RCFM_ERR_ARG, kBatchLimit);
+        RC_REQUIRE(mode == RCFM_AGC_PEAK || mode == RCFM_AGC_CARRIER, RCFM_ERR_ARG, "unknown AGC mode");
+        RC_REQUIRE(std::isfinite(decay_samples) && decay_samples > 0.0, RCFM_ERR_ARG, "AGC decay_samples must be finite and > 0");
+        RC_REQUIRE(std::isfinite(level) && level > 0.f, RCFM_ERR_ARG, "AGC level must be finite and > 0");
+        RC_REQUIRE(std::isfinite(floor) && floor >= 0.f, RCFM_ERR_ARG, "AGC floor must be finite and >= 0");
+        {   // a row is staged whole before it is stored, so in place works; a shifted overlap would read rows already written
+            const char* xb = static_cast<const char*>(v);
+            const char* yb = static_cast<const char*>(audio);
+            const size_t bytes = (size_t)C * (size_t)n * sizeof(float);
+            RC_REQUIRE(xb == yb || xb + bytes <= yb || yb + bytes <= xb, RCFM_ERR_ARG,
+                       "rcfm_agc runs in place (audio == v) or on separate arrays: partial overlap");
+        }
+        launch_agc_tail(mode, static_cast<const float*>(v), static_cast<float*>(audio), n, C,
+                        agc_params(decay_samples, level, floor), static_cast<float*>(state), as_stream(stream));
     });
 }
 

@@ -23,6 +23,7 @@ RCFM_FM, RCFM_MFM, RCFM_WBFM = 0, 1, 2
 RCFM_AM = 3
 RCFM_USB, RCFM_LSB = 5, 6          # 4 is unassigned (include/rcfm.h)
 RCFM_SSB_LEVEL = 0.25
+RCFM_AGC_PEAK, RCFM_AGC_CARRIER = 0, 1   # rcfm_agc
 RCFM_OPT_LDS_CHAIN, RCFM_OPT_FUSED_TILES, RCFM_OPT_PHASE_LINK, RCFM_OPT_NARROW_TILES, RCFM_OPT_STATE_FENCE = 1, 2, 3, 4, 5   # rcfm_demod_set_option
 RCFM_OPT_PILOT_CHAIN, RCFM_OPT_DECIM_TILE, RCFM_OPT_LDS_DEEMPH, RCFM_OPT_PILOT_BLOCKED, RCFM_OPT_GRAPH = 6, 7, 8, 9, 10
 RCFM_OPT_SSB_DIRECT = 11
@@ -78,6 +79,9 @@ SIGNATURES = {
     "rcfm_demod_get_state": [_vp, _fp, _vp],
     "rcfm_demod_set_state": [_vp, _fp, _vp],
     "rcfm_demod_get_taps": [_vp, _fp, _fp],
+    "rcfm_demod_set_agc": [_vp, _dbl, ctypes.c_float, ctypes.c_float],
+    "rcfm_demod_get_agc_state": [_vp, _fp, _vp],
+    "rcfm_demod_set_agc_state": [_vp, _fp, _vp],
     "rcfm_demod_bind_state": [_vp, _vp, _i, _i, _vp],
     "rcfm_demod_set_option": [_vp, _i, _i],
     "rcfm_demod_get_option": [_vp, _i, ctypes.POINTER(_i)],
@@ -108,6 +112,7 @@ SIGNATURES = {
     "rcfm_resampler_destroy": [_vp],
     "rcfm_filtfilt": [_i, _i, _fp, _i, _vp, _vp, _vp],
     "rcfm_lfilter_fir": [_i, _i, _fp, _i, _vp, _vp, _vp, _vp],
+    "rcfm_agc": [_i, _i, _i, _dbl, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp],
     "rcfm_hilbert": [_i, _i, _vp, _vp, _vp],
     "rcfm_pll_phase": [_vp, _sz, _dbl, _i, _vp, _vp],
     "rcfm_discriminator": [_i, _i, _vp, _vp, _vp],

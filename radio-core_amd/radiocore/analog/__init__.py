@@ -6,6 +6,7 @@ from radiocore.analog.mfm import *
 from radiocore.analog.fm import *
 from radiocore.analog.am import *
 from radiocore.analog.ssb import *
+from radiocore.analog.agc import *
 from radiocore.analog.subcarrier import *
 from radiocore.analog.deemphasis import *
 from radiocore.analog.decimate import *

@@ -18,6 +18,8 @@ class Demodulator(Injector):
 
     _KIND = None
     _CHANNELS = 1
+    _AGC_LEVEL = None      # AM, USB, LSB: the default level of an AGC (radiocore.AGC); None: the class takes no AGC
+    _agc = None            # (decay_samples, level, floor) of rcfm_demod_set_agc, or None: off
 
     def __init__(self, input_size, output_size, deemphasis=75e-6, cuda=False, batch=1, chunk=0):
         self._cuda = cuda
@@ -50,6 +52,8 @@ class Demodulator(Injector):
                 hip.check(self._lib.rcfm_demod_create(self._KIND, self._batch, self._input_size, self._output_size,
                                                       self._tau, self._chunk, ctypes.byref(h)))
             self._h = hip.Handle(h, self._lib.rcfm_demod_destroy)
+            if self._agc is not None:                # before the binding: set_agc gives the handle a state of its own
+                hip.check(self._lib.rcfm_demod_set_agc(h, *self._agc))
             self._apply_binding(move_history=0)      # new handle: the batched caller has carried the state so far
         return self._h
 
@@ -69,6 +73,24 @@ class Demodulator(Injector):
             return
         hip.check(self._lib.rcfm_demod_bind_state(self._h.value, owner.value, self._binding[1], int(move_history),
                                                   hip.stream()))
+
+    def _set_agc(self, agc):
+        # AM / USB / LSB constructors: what rcfm_demod_set_agc would refuse raises ValueError here
+        if agc is None:
+            return
+        if not hasattr(agc, "_settings"):
+            raise ValueError("agc takes a radiocore.AGC (or None)")
+        self._agc = agc._settings(self._output_size, self._AGC_LEVEL)
+
+    def agc_state(self):
+        """The AGC follower's value per channel, float32 [batch]: the peak (USB / LSB) or carrier (AM) level after
+        the last buffer, -1 before the first.  ValueError for a demodulator without ``agc``."""
+        if self._agc is None:
+            raise ValueError("this demodulator has no AGC")
+        out = np.zeros(self._batch, np.float32)
+        hip.check(self._lib.rcfm_demod_get_agc_state(self._handle.value,
+                                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), hip.stream()))
+        return out
 
     @property
     def channels(self):
@@ -93,7 +115,7 @@ class Demodulator(Injector):
         return audio
 
     def reset(self):
-        """Back to the reference's freshly constructed filter state."""
+        """Back to the reference's freshly constructed filter state (and an AGC without history)."""
         hip.check(self._lib.rcfm_demod_reset_state(self._handle.value, hip.stream()))
 
     def state(self):

@@ -12,10 +12,19 @@ class USB(Demodulator):
 
     Same constructor as FM / MFM / AM; `deemphasis` is accepted and unused, and no state is carried from buffer to
     buffer.  A silent channel (RMS not positive) gives zeros.  Output: float32 (output_size, 1).  Inside a Tuner
-    (`run_all` / `run_each`) the audio comes straight from the loaded wideband spectrum."""
+    (`run_all` / `run_each`) the audio comes straight from the loaded wideband spectrum.
+
+    ``agc=radiocore.AGC(...)``: a peak follower carried from buffer to buffer replaces the buffer's RMS
+    (``e = max(|v|, lambda e)``, audio ``level v / max(e, floor)``): a pause no longer raises the gain of its buffer, and
+    the gain does not step at buffer boundaries; ``agc_state()`` reads the follower."""
 
     _KIND = hip.RCFM_USB
     _CHANNELS = 1
+    _AGC_LEVEL = hip.RCFM_SSB_LEVEL
+
+    def __init__(self, input_size, output_size, deemphasis=75e-6, cuda=False, batch=1, chunk=0, agc=None):
+        super().__init__(input_size, output_size, deemphasis, cuda, batch, chunk)
+        self._set_agc(agc)
 
     def _shape(self, audio):
         return audio[0] if self._batch == 1 else audio

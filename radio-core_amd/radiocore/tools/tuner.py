@@ -19,6 +19,13 @@ __all__ = ["Tuner", "Channel"]
 _KINDS = {"FM": hip.RCFM_FM, "MFM": hip.RCFM_MFM, "WBFM": hip.RCFM_WBFM, "AM": hip.RCFM_AM,
           "USB": hip.RCFM_USB, "LSB": hip.RCFM_LSB}
 _STATELESS = (hip.RCFM_FM, hip.RCFM_AM, hip.RCFM_USB, hip.RCFM_LSB)    # kinds without de-emphasis state: nothing to bind or fence
+                                                                       # (unless AM / USB / LSB carry an AGC: its state is bound and fenced)
+
+
+def _key_agc(key):
+    """The AGC setting (decay_samples, level, floor) a _batched key ends with, or None."""
+    last = key[-1]
+    return last[1] if isinstance(last, tuple) and last[:1] == ("agc",) else None
 
 
 @dataclass
@@ -468,7 +475,7 @@ class Tuner(Injector):
                 while g is not None and j < first + count and int(self._bounds[j].bandwidth) == bw and \
                         self._geometry(self._bounds[j].demodulator) == g:
                     j += 1
-                groups.append((i, j - i) + (g if g is not None else (None, None, None, None)))
+                groups.append((i, j - i) + (g if g is not None else (None, None, None, None)))     # (+ the AGC setting, if any)
                 i = j
             self._plan = (key, groups, first, count)
         return self._plan[1], self._plan[2], self._plan[3]
@@ -493,17 +500,17 @@ class Tuner(Injector):
         geo = self._plan_uniform()     # ALL channels of the tuner, not only the shard's
         if geo is None:
             raise ValueError("run_all needs one demodulator class and geometry for all channels")
-        kind, B, A, tau = geo
+        kind, B, A, tau = geo[:4]
         ch = 2 if kind == hip.RCFM_WBFM else 1
         audio = hip.empty((count, A, ch), self._torch.float32)
-        hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk), first, count,
+        hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk, *geo[4:]), first, count,
                                               hip.ptr(audio), hip.stream()))
         self._open = [self._squelch_group(handle, first, count, audio)] if self._squelch is not None and count else None
         return audio
 
     def _plan_uniform(self):
-        """(kind, B, A, tau) when every channel of the tuner carries the same demodulator class and geometry,
-        else None; cached per channel-list version."""
+        """(kind, B, A, tau) -- plus the AGC setting where there is one -- when every channel of the tuner carries the
+        same demodulator class and geometry, else None; cached per channel-list version."""
         if self._uniform[0] != self._version:
             geo = {self._geometry(c.demodulator) for c in self._bounds}
             self._uniform = (self._version, next(iter(geo)) if len(geo) == 1 and None not in geo else None)
@@ -527,12 +534,12 @@ class Tuner(Injector):
         groups, first, count = self._launch_plan()
         blocks = []
         masks = [] if self._squelch is not None else None
-        for i, n, kind, B, A, tau in groups:
+        for i, n, kind, B, A, tau, *agc in groups:
             if kind is None:
                 raise ValueError("run_each needs an FM, MFM, WBFM, AM, USB or LSB demodulator on every channel")
             ch = 2 if kind == hip.RCFM_WBFM else 1
             audio = hip.empty((n, A, ch), self._torch.float32)
-            hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, 0), i, n,
+            hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, 0, *agc), i, n,
                                                   hip.ptr(audio), hip.stream()))
             if masks is not None:
                 masks.append(self._squelch_group(handle, i, n, audio))
@@ -552,11 +559,14 @@ class Tuner(Injector):
         kind = _KINDS.get(type(demod).__name__)
         if kind is None:
             return None
-        return kind, demod._input_size, demod._output_size, demod._tau
+        geo = (kind, demod._input_size, demod._output_size, demod._tau)
+        agc = getattr(demod, "_agc", None)          # (decay_samples, level, floor); off: the four-tuple as ever
+        return geo if agc is None else geo + (agc,)
 
     def reset_states(self):
-        """Every channel's de-emphasis state back to the reference's freshly constructed filters (deemphasis.py:48-49):
-        the batched handles of run_all / run_each, whose slots the channels' demodulator objects share."""
+        """Every channel's de-emphasis state back to the reference's freshly constructed filters (deemphasis.py:48-49),
+        and every AGC back to "no history": the batched handles of run_all / run_each, whose slots the channels'
+        demodulator objects share."""
         for h in self._batched.values():
             hip.check(self._lib.rcfm_demod_reset_state(h.value, hip.stream()))
 
@@ -570,16 +580,20 @@ class Tuner(Injector):
         run_all / run_each."""
         self._kernel_options = (bool(lds_chain), bool(fused_tiles), bool(phase_link), int(narrow_tiles), bool(ssb_direct))
 
-    def _batched_demod(self, kind, B, A, tau, chunk):
-        # one handle per geometry, sized for all channels: rcfm_pipeline_run addresses the channels of tuner and
-        # demodulator by the same index, so the per-channel state survives regrouping
+    def _batched_demod(self, kind, B, A, tau, chunk, agc=None):
+        # one handle per geometry (and AGC setting), sized for all channels: rcfm_pipeline_run addresses the channels of
+        # tuner and demodulator by the same index, so the per-channel state survives regrouping
         opts = getattr(self, "_kernel_options", (True, True, True, 1, True))
         key = (kind, len(self._bounds), B, A, tau, int(chunk)) + ((opts,) if opts != (True, True, True, 1, True) else ())
+        if agc is not None:
+            key += (("agc", agc),)
         if key not in self._batched:
             h = ctypes.c_void_p()
             with hip.bound(self._arena):
                 hip.check(self._lib.rcfm_demod_create(kind, len(self._bounds), B, A, tau, int(chunk), ctypes.byref(h)))
             self._batched[key] = hip.Handle(h, self._lib.rcfm_demod_destroy)
+            if agc is not None:                   # before the binding: set_agc gives the handle a state of its own
+                hip.check(self._lib.rcfm_demod_set_agc(h, *agc))
             for opt, on in zip((hip.RCFM_OPT_LDS_CHAIN, hip.RCFM_OPT_FUSED_TILES, hip.RCFM_OPT_PHASE_LINK), opts[:3]):
                 if not on:
                     hip.check(self._lib.rcfm_demod_set_option(h, opt, 0))
@@ -588,7 +602,7 @@ class Tuner(Injector):
             if opts[3] != 1:   # (rcfm_pipeline_run hands the same setting to the tuner's inverse FFT of each chunk)
                 hip.check(self._lib.rcfm_demod_set_option(h, hip.RCFM_OPT_NARROW_TILES, opts[3]))
             self._bind_states(key, self._batched[key])
-            if self._state_fence and kind not in _STATELESS:    # after the binding: the fence travels with the state buffer
+            if self._state_fence and (kind not in _STATELESS or agc is not None):    # after the binding: the fence travels with the state buffer
                 hip.check(self._lib.rcfm_demod_set_option(h, hip.RCFM_OPT_STATE_FENCE, 1))
         elif self._bound_version.get(key) != self._version:
             self._bind_states(key, self._batched[key])
@@ -601,12 +615,14 @@ class Tuner(Injector):
         what it has carried so far), and further batched handles of the same geometry (another `chunk`) share the
         first one's buffer.  Mixing ``ch.demodulator.run(tuner.run(i))`` and ``run_all()`` across buffers then gives
         what the reference's loop gives.  O(C) Python, once per change of the channel list; a demodulator whose own
-        librcfm handle does not exist yet (it is created on first use) binds when it does; FM, AM, USB and LSB carry no state."""
+        librcfm handle does not exist yet (it is created on first use) binds when it does; FM, AM, USB and LSB carry no
+        state -- unless AM / USB / LSB run an AGC, whose follower is bound the same way, per AGC setting."""
         kind, C, B, A, tau = key[:5]
+        agc = _key_agc(key)
         self._bound_version[key] = self._version
-        if kind in _STATELESS:
+        if kind in _STATELESS and agc is None:
             return
-        owner_key = (kind, C, B, A, tau)
+        owner_key = (kind, C, B, A, tau) + ((agc,) if agc is not None else ())
         owner = self._state_owner.get(owner_key)
         if owner is None:
             self._state_owner[owner_key] = handle
@@ -614,7 +630,7 @@ class Tuner(Injector):
             hip.check(self._lib.rcfm_demod_bind_state(handle.value, owner.value, 0, 0, hip.stream()))   # the owner has the history
         if getattr(self, "_is_lane", False):
             return                            # the channels' demodulator objects stay bound to the base tuner's handle
-        geo = (kind, B, A, tau)
+        geo = (kind, B, A, tau) + ((agc,) if agc is not None else ())
         seen = set()
         for c in self._bounds:
             d = c.demodulator
@@ -630,7 +646,7 @@ class Tuner(Injector):
         that touches the shared de-emphasis state waits for the previous one (rcfm_demod_set_option, RCFM_OPT_STATE_FENCE)."""
         self._state_fence = True
         for key, h in self._batched.items():
-            if key[0] not in _STATELESS:
+            if key[0] not in _STATELESS or _key_agc(key) is not None:
                 hip.check(self._lib.rcfm_demod_set_option(h.value, hip.RCFM_OPT_STATE_FENCE, 1))
 
     def _lane_clone(self):

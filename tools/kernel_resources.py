@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / occupancy table of one translation unit (compiler view):
     tools/kernel_resources.py radio-core_amd/csrc/fft_engine.hip [filter-substring] [-DFLAG ...]
-Runs hipcc -Rpass-analysis=kernel-resource-usage for gfx950 and demangles the names."""
+Runs hipcc -Rpass-analysis=kernel-resource-usage for gfx950 and demangles the names.
+    tools/kernel_resources.py radio-core_amd/csrc/agc.hip k_agc_tail
+is the AGC tail in its four forms (mode x 16-byte / scalar accesses): at most 86 VGPRs, no scratch, 32.1 KiB of LDS, four
+workgroups per CU."""
 import re
 import subprocess
 import sys
