@@ -47,7 +47,9 @@ extern "C" {
                             rcfm_tuner_carriers and rcfm_tuner_retune added (new symbols only, nothing existing changed);
                             rcfm_subcarrier_* and rcfm_pipeline_subcarrier added (new symbols only, nothing existing changed);
                             rcfm_agc, rcfm_demod_set_agc and rcfm_demod_get / set_agc_state added (new symbols only; a handle
-                            that never calls rcfm_demod_set_agc launches what it launched before) */
+                            that never calls rcfm_demod_set_agc launches what it launched before);
+                            rcfm_tuner_load_raw and rcfm_iq_convert added (new symbols only; rcfm_tuner_load launches what it
+                            launched before) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -117,6 +119,22 @@ int rcfm_tuner_create(int64_t n, int nch, const int64_t* roll_host, const int32_
                       rcfm_tuner_t* out);
 /* Tuner.load, tuner.py:126-138: X = FFT_n(x), kept by the handle. x: [n] complex64. */
 int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream);
+/* Raw integer IQ as receivers deliver it (no reference counterpart: the reference's load takes complex64 only): n pairs
+ * interleaved I, Q, little-endian, full scale 1.0.  Every conversion is exact in float32:
+ *   RCFM_IQ_CS16  int16  (Airspy, the USRP wire format, most files)   (float)i * 2^-15
+ *   RCFM_IQ_CS8   int8   (HackRF)                                     (float)i * 2^-7
+ *   RCFM_IQ_CU8   uint8  (RTL-SDR; the centre is 127.5)               ((float)u - 127.5f) * 2^-7   (255 -> 0.99609375) */
+enum { RCFM_IQ_CS16 = 1, RCFM_IQ_CS8 = 2, RCFM_IQ_CU8 = 3 };
+/* rcfm_tuner_load of a raw buffer, x: [n][2] of the format's integer type on the device: the spectrum (halos, shard window,
+ * held bins) is bit for bit that of rcfm_tuner_load of the converted samples, and the same refusals apply.  Where the
+ * handle's wideband FFT runs on the engine, the conversion rides on the first pass's load (the buffer is read once, at 4
+ * or 2 bytes per sample, and complex64 samples never exist in memory); otherwise (lengths that run on rocFFT,
+ * RCFM_FFT=rocfft) rcfm_iq_convert fills a scratch buffer of the handle, reserved by the first such load, and the
+ * complex64 load runs on that.  Any other format: RCFM_ERR_ARG before any device call. */
+int rcfm_tuner_load_raw(rcfm_tuner_t t, int format, const void* x, void* stream);
+/* The conversion alone, for hosts that feed rcfm_resampler_run / rcfm_demod_run or code of their own: n pairs at `in`
+ * (device memory, aligned for one integer of the format -- not for a pair) -> out_c64 [n] complex64.  n = 0 is a no-op. */
+int rcfm_iq_convert(int format, size_t n, const void* in, void* out_c64, void* stream);
 /* Multi-GPU sharding (no reference counterpart: the reference has one device; its loop over all channels is
  * examples/multi_fm_server.py:100-106).  A rank that will only run channels [first, first + count) declares
  * it before rcfm_tuner_load: the last pass of the wideband FFT then stores only the part of the spectrum

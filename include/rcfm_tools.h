@@ -52,6 +52,10 @@ enum { RCFM_TUNER_OPT_NARROW_TILES = 1,
         * default plan.  Takes effect with the next rcfm_tuner_load; same spectrum within float32 rounding. */
        RCFM_TUNER_OPT_ALIGNED_PLAN = 2 };
 int rcfm_tuner_set_option(rcfm_tuner_t t, int option, int value);
+/* Which way rcfm_tuner_load_raw (rcfm.h) takes on this handle for `format`: *route = 1, the conversion rides on the first
+ * pass of the wideband FFT; 0, rcfm_iq_convert runs into the handle's scratch in front of the unchanged complex64 load
+ * (what a test needs to know which form it compared).  No device call. */
+int rcfm_tuner_load_route(rcfm_tuner_t t, int format, int* route);
 
 /* Which forms of the chain a handle may use (no reference counterpart: the reference has one form of everything).
  * All default to 1.  The results do not depend on them beyond float32 rounding -- tests/test_hip_configs.py compares

@@ -230,6 +230,11 @@ struct rcfm_tuner_s {
     std::unique_ptr<rcfm::FftPlan> forward;    // rocFFT fallback for lengths outside the engine
     std::unique_ptr<rcfm::FftEngine> forward_engine;
     rcfm::DeviceBuffer forward_tmp;            // engine: the last pass cannot run in place
+    rcfm::DeviceBuffer raw_c64;                // rcfm_tuner_load_raw without the engine: the converted buffer, [n] complex64,
+                                               // reserved by the first such load (a buffer of its own: forward_tmp and the
+                                               // rocFFT workspace are busy while the load reads it)
+    // rcfm_tuner_load_raw: the conversion rides on the first pass of the wideband FFT (every engine plan has two or more)
+    bool raw_fused() const { return forward_engine != nullptr && forward_engine->npass() >= 2; }
     // RCFM_TUNER_OPT_ALIGNED_PLAN: the default plan's pass lengths in the order whose LAST pass stores aligned segments,
     // in the padded-rows layout (fft_engine.h, layout 2) -- N = 2.4e8 = 640 x 625 x 600 with 608-point scratch rows.  Its
     // first intermediate lives in the handle's own spectrum storage (sized for it), so an attached storage runs the

@@ -134,8 +134,11 @@ class FftEngine {
     // tmp2 (optional, tmp_stride() elements per signal, distinct from everything else): a second scratch array -- a
     // three-pass plan then runs in -> tmp2 -> tmp -> out with no pass in place (what the padded-rows layout, whose
     // intermediates do not fit `out`, needs to ping-pong).
+    // in_format (forward transforms only): 0 = `in` holds complex64, else RCFM_IQ_* (include/rcfm.h) -- `in` then points
+    // at n raw integer pairs per signal, which the FIRST pass converts as it loads them (fft_kernel.h, LoadIq16 / LoadIq8 /
+    // LoadIqU8); every later pass and every store is the complex64 transform's.
     void c2c(const float2* in, float2* out, float2* tmp, int batch, bool inverse, float scale,
-             hipStream_t stream, const FftRowWindow* keep = nullptr, float2* tmp2 = nullptr) const;
+             hipStream_t stream, const FftRowWindow* keep = nullptr, float2* tmp2 = nullptr, int in_format = 0) const;
     int64_t row_length() const { return desc_.pass[0].L; }   // n_1
     FftPassDev pass_dev(int t, int64_t in_batch, int64_t out_batch, bool blocked = false) const;
     static size_t lds_bytes(int L);

@@ -409,9 +409,11 @@ FftPassDev FftEngine::pass_dev(int t, int64_t in_batch, int64_t out_batch, bool 
 }
 
 void FftEngine::c2c(const float2* in, float2* out, float2* tmp, int batch, bool inverse, float scale,
-                    hipStream_t stream, const FftRowWindow* keep, float2* tmp2) const {
+                    hipStream_t stream, const FftRowWindow* keep, float2* tmp2, int in_format) const {
     if (batch <= 0) return;
     const int np = desc_.npass;
+    RC_REQUIRE(in_format == 0 || (!inverse && np >= 2 && in_format >= RCFM_IQ_CS16 && in_format <= RCFM_IQ_CU8), RCFM_ERR_ARG,
+               "raw integer input: forward transforms of two or more passes, formats RCFM_IQ_*");
     const int64_t n = desc_.n;
     using namespace fftk;
     const int64_t ts = desc_.tmp_stride;
@@ -453,6 +455,12 @@ void FftEngine::c2c(const float2* in, float2* out, float2* tmp, int batch, bool 
             StorePlainT<false> st{mid(t), 1.0f};
             if (first && inverse)
                 launch_fft_pass<kStridedOnly>(dev, batch, LoadPlainT<true>{src}, st, stream);
+            else if (first && in_format == RCFM_IQ_CS16)
+                launch_fft_pass<kStridedOnly>(dev, batch, LoadIq16{reinterpret_cast<const uint32_t*>(src)}, st, stream);
+            else if (first && in_format == RCFM_IQ_CS8)
+                launch_fft_pass<kStridedOnly>(dev, batch, LoadIq8{reinterpret_cast<const uint16_t*>(src)}, st, stream);
+            else if (first && in_format == RCFM_IQ_CU8)
+                launch_fft_pass<kStridedOnly>(dev, batch, LoadIqU8{reinterpret_cast<const uint16_t*>(src)}, st, stream);
             else
                 launch_fft_pass<kStridedOnly>(dev, batch, LoadPlainT<false>{src}, st, stream);
         }

@@ -1549,6 +1549,46 @@ struct LoadPlainT {
     }
 };
 
+// Raw integer IQ (include/rcfm.h, RCFM_IQ_*) as the input of a transform's first pass: element base + off is one
+// interleaved pair, 4 bytes (int16) or 2 (int8, uint8).  fetch issues that one load and carries the bits in .x of the
+// float2 it must return (a move, no arithmetic: a bit pattern that happens to be a NaN survives it); post unpacks and
+// scales by the power of two, which is exact in float32 -- the tile computes on the values LoadPlainT would have read
+// from the converted buffer.
+__device__ __forceinline__ float2 iq_bits(unsigned raw) { return make_float2(__uint_as_float(raw), 0.f); }
+
+struct LoadIq16 {
+    const uint32_t* in;
+    __device__ __forceinline__ float2 fetch(const LineId&, int, int64_t base, unsigned off) const {
+        return iq_bits(in[base + off]);
+    }
+    __device__ __forceinline__ float2 post(const LineId&, int, float2 v) const {
+        const unsigned raw = __float_as_uint(v.x);
+        return make_float2((float)(int16_t)(raw & 0xffffu) * 0x1p-15f, (float)(int16_t)(raw >> 16) * 0x1p-15f);
+    }
+};
+
+struct LoadIq8 {
+    const uint16_t* in;
+    __device__ __forceinline__ float2 fetch(const LineId&, int, int64_t base, unsigned off) const {
+        return iq_bits(in[base + off]);
+    }
+    __device__ __forceinline__ float2 post(const LineId&, int, float2 v) const {
+        const unsigned raw = __float_as_uint(v.x);
+        return make_float2((float)(int8_t)(raw & 0xffu) * 0x1p-7f, (float)(int8_t)(raw >> 8) * 0x1p-7f);
+    }
+};
+
+struct LoadIqU8 {
+    const uint16_t* in;
+    __device__ __forceinline__ float2 fetch(const LineId&, int, int64_t base, unsigned off) const {
+        return iq_bits(in[base + off]);
+    }
+    __device__ __forceinline__ float2 post(const LineId&, int, float2 v) const {
+        const unsigned raw = __float_as_uint(v.x);
+        return make_float2(((float)(raw & 0xffu) - 127.5f) * 0x1p-7f, ((float)(raw >> 8) - 127.5f) * 0x1p-7f);
+    }
+};
+
 template <bool SWAP>
 struct StorePlainT {
     float2* out;
@@ -1653,6 +1693,9 @@ constexpr int tile_threads(int L) {   // (RG = T / W butterfly rows per sweep is
 template <class T> struct is_plain_functor : std::false_type {};
 template <bool S> struct is_plain_functor<LoadPlainT<S>> : std::true_type {};
 template <bool S> struct is_plain_functor<StorePlainT<S>> : std::true_type {};
+template <> struct is_plain_functor<LoadIq16> : std::true_type {};
+template <> struct is_plain_functor<LoadIq8> : std::true_type {};
+template <> struct is_plain_functor<LoadIqU8> : std::true_type {};
 template <> struct is_plain_functor<StoreRowWindow> : std::true_type {};
 
 // Which pass kinds a functor pair is ever used with (prunes template instantiations).

@@ -186,5 +186,9 @@ void launch_power_spectrum(const float2* X, int64_t N, int64_t s0, int64_t L, in
 // rows of closed channels of audio [count][row] float32 (may be null) := 0, rows of open channels untouched.
 void launch_squelch(const float* power, const float* threshold, int count, size_t row, float* audio, uint8_t* open,
                     hipStream_t stream);
+// Raw integer IQ (iq.hip; include/rcfm.h, RCFM_IQ_*): n interleaved pairs at `in` (aligned for one integer) -> out [n]
+// complex64, each value exactly the format's integer times its power of two.  n = 0: nothing is launched.
+bool iq_format_ok(int format);
+void launch_iq_convert(int format, size_t n, const void* in, float2* out, hipStream_t stream);
 
 }  // namespace rcfm

@@ -357,14 +357,26 @@ int rcfm_tuner_create(int64_t n, int nch, const int64_t* roll_host, const int32_
     });
 }
 
-int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream) {
+// rcfm_tuner_load (format 0: x holds complex64) and rcfm_tuner_load_raw (RCFM_IQ_*: x holds integer pairs).
+static int tuner_load(rcfm_tuner_t t, int format, const void* x, void* stream) {
     return guarded([&] {
+        RC_REQUIRE(format == 0 || iq_format_ok(format), RCFM_ERR_ARG,
+                   "unknown IQ format (RCFM_IQ_CS16, RCFM_IQ_CS8, RCFM_IQ_CU8)");
         RC_REQUIRE(t && x, RCFM_ERR_ARG, "NULL argument");
+        // (the first pass loads a pair as one 4- or 2-byte word)
+        RC_REQUIRE(format == 0 || !t->raw_fused() || (uintptr_t)x % (format == RCFM_IQ_CS16 ? 4 : 2) == 0, RCFM_ERR_ARG,
+                   "misaligned buffer: rcfm_tuner_load_raw reads whole I, Q pairs");
         ArenaScope scope(t->arena);
         RC_REQUIRE(!t->ext_window, RCFM_ERR_STATE,
                    "rcfm_tuner_load needs storage for the whole spectrum: a window is attached (rcfm_tuner_attach_window)");
         {
             StageTimer tm(ST_TUNER_FFT, as_stream(stream));
+            if (format != 0 && !t->raw_fused()) {   // no first pass to ride on: convert, then the complex64 load
+                t->raw_c64.reserve(sizeof(float2) * (size_t)t->n);
+                launch_iq_convert(format, (size_t)t->n, x, t->raw_c64.as<float2>(), as_stream(stream));
+                x = t->raw_c64.get();
+                format = 0;
+            }
             bool halo_done = false;
             if (t->forward_engine) {
                 // the last pass writes the halos itself (bins near both ends are stored twice): no copy launches
@@ -376,7 +388,7 @@ int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream) {
                 halo_done = t->halo > 0;
                 // (aligned plan: x -> the spectrum storage as scratch -> forward_tmp -> the spectrum, no pass in place)
                 eng.c2c(static_cast<const float2*>(x), t->spectrum(), t->forward_tmp.as<float2>(), 1, false, 1.0f,
-                        as_stream(stream), &w, al ? t->X.as<float2>() : nullptr);
+                        as_stream(stream), &w, al ? t->X.as<float2>() : nullptr, format);
             } else {
                 t->forward_work.reserve(t->forward->work_bytes());
                 t->forward->exec(const_cast<void*>(x), t->spectrum(), t->forward_work.get(), as_stream(stream));
@@ -397,6 +409,21 @@ int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream) {
             const int64_t f0 = (al ? *t->forward_aligned : *t->forward_engine).row_length(), rows = t->n / f0;
             t->set_held((int64_t)w.lo * f0, (((int64_t)w.hi - w.lo + rows) % rows + 1) * f0);
         }
+    });
+}
+
+int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream) { return tuner_load(t, 0, x, stream); }
+
+int rcfm_tuner_load_raw(rcfm_tuner_t t, int format, const void* x, void* stream) {
+    if (format == 0) format = -1;   // 0 is tuner_load's complex64, not a format of this entry point
+    return tuner_load(t, format, x, stream);
+}
+
+int rcfm_tuner_load_route(rcfm_tuner_t t, int format, int* route) {
+    return guarded([&] {
+        RC_REQUIRE(iq_format_ok(format), RCFM_ERR_ARG, "unknown IQ format (RCFM_IQ_CS16, RCFM_IQ_CS8, RCFM_IQ_CU8)");
+        RC_REQUIRE(t && route, RCFM_ERR_ARG, "NULL argument");
+        *route = t->raw_fused() ? 1 : 0;
     });
 }
 

@@ -27,6 +27,7 @@ RCFM_AGC_PEAK, RCFM_AGC_CARRIER = 0, 1   # rcfm_agc
 RCFM_OPT_LDS_CHAIN, RCFM_OPT_FUSED_TILES, RCFM_OPT_PHASE_LINK, RCFM_OPT_NARROW_TILES, RCFM_OPT_STATE_FENCE = 1, 2, 3, 4, 5   # rcfm_demod_set_option
 RCFM_OPT_PILOT_CHAIN, RCFM_OPT_DECIM_TILE, RCFM_OPT_LDS_DEEMPH, RCFM_OPT_PILOT_BLOCKED, RCFM_OPT_GRAPH = 6, 7, 8, 9, 10
 RCFM_OPT_SSB_DIRECT = 11
+RCFM_IQ_CS16, RCFM_IQ_CS8, RCFM_IQ_CU8 = 1, 2, 3                  # rcfm_tuner_load_raw, rcfm_iq_convert
 RCFM_TUNER_OPT_NARROW_TILES, RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                                # rcfm_tuner_set_option
 
 _ERR_SIZE, _ERR_INDEX, _ERR_RUNTIME, _ERR_ARG, _ERR_STATE = -1, -2, -3, -4, -5
@@ -57,6 +58,9 @@ SIGNATURES = {
     "rcfm_arena_destroy": [_vp],
     "rcfm_tuner_create": [_i64, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_vp)],
     "rcfm_tuner_load": [_vp, _vp, _vp],
+    "rcfm_tuner_load_raw": [_vp, _i, _vp, _vp],
+    "rcfm_tuner_load_route": [_vp, _i, ctypes.POINTER(_i)],
+    "rcfm_iq_convert": [_i, _sz, _vp, _vp, _vp],
     "rcfm_tuner_shard": [_vp, _i, _i],
     "rcfm_tuner_run": [_vp, _i, _i, _vp, _vp],
     "rcfm_tuner_spectrum": [_vp, ctypes.POINTER(_vp)],

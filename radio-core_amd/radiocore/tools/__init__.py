@@ -13,4 +13,4 @@ from radiocore.tools.spectrum import *
 from radiocore.tools.feeder import *
 from radiocore.tools.lanes import *
 from radiocore.tools.arena import *
-from radiocore.tools import rds
+from radiocore.tools import iq, rds

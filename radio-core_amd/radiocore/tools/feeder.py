@@ -36,7 +36,10 @@ class Feeder(Injector):
         super().__init__(True)
         self._size = int(size)
         self._dtype = np.dtype(dtype)
-        tdt = {np.dtype("complex64"): self._torch.complex64, np.dtype("float32"): self._torch.float32}[self._dtype]
+        # (raw integer IQ for Tuner.load_raw: `size` counts integers, two per sample)
+        tdt = {np.dtype("complex64"): self._torch.complex64, np.dtype("float32"): self._torch.float32,
+               np.dtype("int16"): self._torch.int16, np.dtype("int8"): self._torch.int8,
+               np.dtype("uint8"): self._torch.uint8}[self._dtype]
         self._slots = [hip.empty((self._size,), tdt) for _ in range(int(depth))]
         ptrs = (ctypes.c_void_p * len(self._slots))(*[s.data_ptr() for s in self._slots])
         h = ctypes.c_void_p()

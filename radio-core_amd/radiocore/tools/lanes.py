@@ -51,11 +51,12 @@ class Lanes:
     def depth(self) -> int:
         return len(self._tuners)
 
-    def submit(self, input_signal, chunk: int = 0, each: bool = False) -> int:
+    def submit(self, input_signal, chunk: int = 0, each: bool = False, raw: bool = False) -> int:
         """Queue Tuner.load + Tuner.run_all of one buffer on the next lane; returns a ticket for ``result``.
         each=True: Tuner.run_each instead (channels of different classes and geometries; ``result`` then returns its
         list of per-channel arrays).  With ``tuner.set_squelch`` set, the lane queues the levels and the squelch behind
-        its demodulators like ``run_all`` does; ``result(ticket, open_mask=True)`` returns the buffer's mask."""
+        its demodulators like ``run_all`` does; ``result(ticket, open_mask=True)`` returns the buffer's mask.
+        raw=True: ``input_signal`` holds interleaved integer I, Q and the lane loads it with Tuner.load_raw."""
         ticket = self._next
         self._next += 1
         k = ticket % len(self._tuners)
@@ -70,7 +71,7 @@ class Lanes:
             input_signal.record_stream(st)
         with self._torch.cuda.stream(st):
             start = self._event(st) if self._timing else None
-            t.load(input_signal)
+            (t.load_raw if raw else t.load)(input_signal)
             loaded = self._event(st)            # the wideband FFT is the LAST reader of the input buffer
             audio = t._run_each_device() if each else t._run_all_device(chunk)
             ev = self._event(st)

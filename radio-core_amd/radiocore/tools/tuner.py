@@ -12,7 +12,7 @@ from typing import List
 import numpy as np
 
 from radiocore._internal import Injector, hip
-from radiocore.tools import spectrum
+from radiocore.tools import iq, spectrum
 
 __all__ = ["Tuner", "Channel"]
 
@@ -196,18 +196,33 @@ class Tuner(Injector):
         whole=True (multi-GPU, rotating FFT owner): keep every row any channel reads although this process is
         sharded -- the spectrum is about to be handed to the other ranks (sharding.SpectrumRing)."""
         x = hip.to_device(input_signal, self._torch.complex64)
-        n = int(x.shape[0])
+        self._load(x, int(x.shape[0]), whole, lambda h: self._lib.rcfm_tuner_load(h, hip.ptr(x), hip.stream()))
+
+    def load_raw(self, samples, whole=False):
+        """``load`` of a buffer as the receiver delivers it (rcfm_tuner_load_raw; no reference counterpart): a numpy array
+        or torch tensor of interleaved I, Q integers, [N, 2] or [2 N], whose dtype names the format -- int16 (Airspy, USRP
+        wire format), int8 (HackRF) or uint8 (RTL-SDR, centre 127.5) -- full scale 1.0.  The spectrum, and so everything run
+        from it, is bit for bit that of ``load(iq.to_complex64(samples))``; the buffer crosses PCIe and is read by the
+        wideband FFT at 4 or 2 bytes per sample instead of 8, and no complex64 copy of it is made.  ValueError for any other
+        dtype, an odd element count, or an N that is not the tuner's input size."""
+        x, fmt, n = iq.device_pairs(samples)
+        if n != int(self._input_bandwidth):
+            raise ValueError("input_sig size and input_size mismatch")
+        self._load(x, n, whole, lambda h: self._lib.rcfm_tuner_load_raw(h, fmt, hip.ptr(x), hip.stream()))
+
+    def _load(self, x, n, whole, call):
+        # what load and load_raw share: `call(handle)` is the library's load of the device buffer x (n samples)
         h = self._device_tuner(n)
         if self._handle_fine is not self._fine:        # a lane that follows the base tuner's retune, on its own stream
             self._apply_fine(h, self._fine)
         if whole and self._shard is not None:
             hip.check(self._lib.rcfm_tuner_shard(h, 0, len(self._bounds)))
             try:
-                hip.check(self._lib.rcfm_tuner_load(h, hip.ptr(x), hip.stream()))
+                hip.check(call(h))
             finally:      # a failed load must not leave the handle sharded to every channel
                 hip.check(self._lib.rcfm_tuner_shard(h, self._shard[0], self._shard[1]))
         else:
-            hip.check(self._lib.rcfm_tuner_load(h, hip.ptr(x), hip.stream()))
+            hip.check(call(h))
         self._input = x            # keeps the buffer alive until the FFT has consumed it
         self._loaded_size = n
 
