@@ -49,7 +49,8 @@ extern "C" {
                             rcfm_agc, rcfm_demod_set_agc and rcfm_demod_get / set_agc_state added (new symbols only; a handle
                             that never calls rcfm_demod_set_agc launches what it launched before);
                             rcfm_tuner_load_raw and rcfm_iq_convert added (new symbols only; rcfm_tuner_load launches what it
-                            launched before) */
+                            launched before);
+                            rcfm_audio_pack and rcfm_drain_* added (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -399,6 +400,33 @@ int rcfm_subcarrier_run(rcfm_subcarrier_t h, int count, const void* iq, void* ou
 int rcfm_pipeline_subcarrier(rcfm_tuner_t t, rcfm_subcarrier_t h, int first, int count, void* out, void* stream);
 int rcfm_subcarrier_destroy(rcfm_subcarrier_t h);
 
+/* ---- audio egress: the open channels' audio, packed densely as PCM (no reference counterpart) -------------------------
+ * Every route ends in audio [count][row] float32 on the device, row = A ch (the floats_per_channel of rcfm_squelch).  A
+ * publisher wants 16-bit PCM of the channels that are open, and only those should cross PCIe.
+ *
+ * Definition.  open: [count] uint8 as rcfm_squelch writes it, any nonzero byte is open; NULL: every channel is open.
+ *   slot(c)              = the number of open channels below c (channel order is kept)
+ *   n_open               = the number of open channels
+ *   index[slot(c)]       = c                        for every open channel c
+ *   packed[slot(c)][i]   = q(audio[c][i])           for every open channel c, i = 0 .. row-1
+ * The conversion q:
+ *   RCFM_PCM_F32   the 32 bits unchanged (NaN payloads survive); gain is ignored
+ *   RCFM_PCM_S16   y = x * gain, one float32 multiply; NaN -> 0; otherwise round to nearest, ties to even, then clamp to
+ *                  [-32767, 32767]: the range is symmetric (-32768 never appears), +-inf and products that overflow
+ *                  saturate.  gain is finite and in (0, 2^24]: below that bound a float32 denormal times gain rounds to 0
+ *                  whether or not denormals are flushed, so the result does not depend on the denormal mode.
+ * audio: [count][row] float32 device; packed: [count][row] int16 or float32 device, the worst-case capacity; index:
+ * [count] int32 device; n_open: one int32 device.  index and n_open may be NULL, packed may not.  Rows of closed channels
+ * are not read.  Rows >= n_open of packed and entries >= n_open of index are not written.
+ * There are no atomics and every output is a function of the inputs alone: bit-identical from run to run and from stream
+ * to stream.  (The slots come from one scan of the mask into a table the library keeps per stream; the pack reads it.)
+ * RCFM_ERR_ARG, checked before any device call: NULL audio or packed, count < 1 or > 65535, row < 1, an unknown format, a
+ * gain that is not finite or outside (0, 2^24] (RCFM_PCM_S16 only), any overlap of audio [count][row] with packed
+ * [count][row], a pointer not aligned for one element of its type. */
+enum { RCFM_PCM_F32 = 0, RCFM_PCM_S16 = 1 };
+int rcfm_audio_pack(const void* audio, const void* open, int count, size_t row, int format, float gain,
+                    void* packed, void* index, void* n_open, void* stream);
+
 /* ---- host ingest (the step before Tuner.load) -------------------------------- */
 
 /* The reference hands its DSP thread a buffer in mapped / shared memory (cusignal.get_shared_mem at
@@ -422,6 +450,35 @@ int rcfm_feeder_acquire(rcfm_feeder_t f, void* stream, void** dptr);
 int rcfm_feeder_release(rcfm_feeder_t f, void* stream);
 int rcfm_feeder_copied(rcfm_feeder_t f, uint64_t* count);
 int rcfm_feeder_destroy(rcfm_feeder_t f);
+
+/* ---- host egress (the step after rcfm_audio_pack: the publish loop, examples/multi_fm_server.py:103-106) ------------- */
+
+/* The mirror of the feeder.  A drain owns `depth` slots; a slot is device memory for one rcfm_audio_pack -- packed
+ * [max_rows][row_bytes], index [max_rows] int32, n_open -- always plain device memory, never a piece of a bound arena, and
+ * a page-locked host mirror of it.  The header (n_open and index, (1 + max_rows) 4 bytes) and the payload travel on two
+ * copy streams of the drain, so the compute stream never waits for the host, and per buffer the header plus n_open rows
+ * cross PCIe, not max_rows rows.
+ *   begin(&packed, &index, &n_open)   device pointers of the next free slot, to pass to rcfm_audio_pack; RCFM_ERR_STATE
+ *                                     when all slots are in flight
+ *   submit(stream)                    the pack of that slot is queued on `stream`: records an event there, makes the header
+ *                                     stream wait for it and queues the header's copy to the host
+ *   acquire(&n, &index, &rows)        the oldest submitted slot: waits on the host for its header only, queues the copy of
+ *                                     exactly n_open row_bytes payload bytes on the payload stream (nothing when n_open is
+ *                                     0) and waits for it; index_host [n_open] and rows_host [n_open][row_bytes] point
+ *                                     into the page-locked slot and stay valid until release.  RCFM_ERR_STATE with nothing
+ *                                     submitted
+ *   release()                         the slot is free again; RCFM_ERR_STATE without an acquired slot
+ *   destroy()                         synchronises both copy streams before anything is freed
+ * Why two streams: the header copy of buffer i+1 waits for that buffer's kernels; a payload of buffer i queued behind it
+ * on the same stream would wait for them too.
+ * RCFM_ERR_ARG before any device call: a NULL pointer, row_bytes == 0, max_rows < 1 or > 65535, depth < 1 or > 64. */
+typedef struct rcfm_drain_s* rcfm_drain_t;
+int rcfm_drain_create(size_t row_bytes, int max_rows, int depth, rcfm_drain_t* out);
+int rcfm_drain_begin(rcfm_drain_t d, void** packed_dev, void** index_dev, void** n_open_dev);
+int rcfm_drain_submit(rcfm_drain_t d, void* stream);
+int rcfm_drain_acquire(rcfm_drain_t d, int* n_open, const int32_t** index_host, const void** rows_host);
+int rcfm_drain_release(rcfm_drain_t d);
+int rcfm_drain_destroy(rcfm_drain_t d);
 
 /* ---- multi-GPU: the audio gather (the publish step, examples/multi_fm_server.py:103-106) ---------- */
 

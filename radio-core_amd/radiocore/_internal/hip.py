@@ -28,6 +28,8 @@ RCFM_OPT_LDS_CHAIN, RCFM_OPT_FUSED_TILES, RCFM_OPT_PHASE_LINK, RCFM_OPT_NARROW_T
 RCFM_OPT_PILOT_CHAIN, RCFM_OPT_DECIM_TILE, RCFM_OPT_LDS_DEEMPH, RCFM_OPT_PILOT_BLOCKED, RCFM_OPT_GRAPH = 6, 7, 8, 9, 10
 RCFM_OPT_SSB_DIRECT = 11
 RCFM_IQ_CS16, RCFM_IQ_CS8, RCFM_IQ_CU8 = 1, 2, 3                  # rcfm_tuner_load_raw, rcfm_iq_convert
+RCFM_PCM_F32, RCFM_PCM_S16 = 0, 1                                 # rcfm_audio_pack
+RCFM_PACK_SEGMENT = 4096           # elements of a row one workgroup of the pack kernel takes per sweep (csrc/egress_kernel.h, kPackSegment)
 RCFM_TUNER_OPT_NARROW_TILES, RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                                # rcfm_tuner_set_option
 
 _ERR_SIZE, _ERR_INDEX, _ERR_RUNTIME, _ERR_ARG, _ERR_STATE = -1, -2, -3, -4, -5
@@ -103,6 +105,13 @@ SIGNATURES = {
     "rcfm_feeder_release": [_vp, _vp],
     "rcfm_feeder_copied": [_vp, ctypes.POINTER(ctypes.c_uint64)],
     "rcfm_feeder_destroy": [_vp],
+    "rcfm_audio_pack": [_vp, _vp, _i, _sz, _i, ctypes.c_float, _vp, _vp, _vp, _vp],
+    "rcfm_drain_create": [_sz, _i, _i, ctypes.POINTER(_vp)],
+    "rcfm_drain_begin": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)],
+    "rcfm_drain_submit": [_vp, _vp],
+    "rcfm_drain_acquire": [_vp, ctypes.POINTER(_i), ctypes.POINTER(_vp), ctypes.POINTER(_vp)],
+    "rcfm_drain_release": [_vp],
+    "rcfm_drain_destroy": [_vp],
     "rcfm_comm_unique_id": [_vp],
     "rcfm_comm_init_rank": [_i, _i, _vp, ctypes.POINTER(_vp)],
     "rcfm_gather_audio": [_vp, _i, _vp, _sz, _vp, _vp],

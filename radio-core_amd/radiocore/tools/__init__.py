@@ -11,6 +11,7 @@ from radiocore.tools.squelch import *
 from radiocore.tools.afc import *
 from radiocore.tools.spectrum import *
 from radiocore.tools.feeder import *
+from radiocore.tools.egress import *
 from radiocore.tools.lanes import *
 from radiocore.tools.arena import *
 from radiocore.tools import iq, rds

@@ -523,6 +523,49 @@ class Tuner(Injector):
         self._open = [self._squelch_group(handle, first, count, audio)] if self._squelch is not None and count else None
         return audio
 
+    def run_all_packed(self, pcm, numpy_output: bool = True, chunk: int = 0, drain=None):
+        """``run_all`` for a publisher (rcfm_audio_pack; no reference counterpart): the audio of the OPEN channels only,
+        packed densely in channel order in the sample format of ``pcm`` (a ``radiocore.PCM``: int16 at a gain, or float32
+        unchanged).  The launches of ``run_all`` run unchanged -- squelch included when set, and ``open_mask()`` keeps
+        working; with squelch off every channel is open -- and the pack follows them on the same stream.
+
+        Without ``drain``: ``(index int32 [n_open], audio [n_open, A, ch])`` as numpy arrays, row k being channel
+        ``index[k]`` of the run's range; only the n_open rows are copied to the host.  On a ``cuda=True`` tuner
+        ``numpy_output=False`` returns the device tensors ``(index [count], packed [count, A, ch], n_open [1])`` without
+        synchronising; entries and rows from n_open on are not written.
+        With ``drain`` (a ``radiocore.tools.Drain`` of at least ``count`` rows of [A, ch] in pcm's dtype): the packed audio
+        goes into the drain's next free slot and its header's copy is queued; the call returns nothing and does not
+        wait -- ``drain.next()`` hands the buffer out.  RuntimeError when every slot of the drain is in flight, ValueError
+        for a drain of another geometry: both before anything is launched."""
+        self._ready()
+        count, geo = self._launch_plan()[2], self._plan_uniform()
+        if count < 1:
+            raise ValueError("run_all_packed needs at least one channel")
+        if drain is not None and geo is not None:          # refused before anything runs (a run advances the de-emphasis state)
+            shape = (geo[2], 2 if geo[0] == hip.RCFM_WBFM else 1)
+            if drain.rows < count or drain.row_shape != shape or drain.dtype != pcm.dtype:
+                raise ValueError("the drain holds %d rows of %s %s, this run packs %d rows of %s %s"
+                                 % (drain.rows, drain.row_shape, drain.dtype, count, shape, pcm.dtype))
+        if drain is not None:
+            packed, index, n_open = drain._begin()         # ... and so is a drain with every slot in flight
+        audio = self._run_all_device(chunk)
+        row = int(audio.shape[1]) * int(audio.shape[2])
+        mask = self._open[0] if self._open else None
+        args = (hip.ptr(audio), hip.ptr(mask) if mask is not None else None, count, row, pcm.format, pcm.gain)
+        if drain is not None:
+            hip.check(self._lib.rcfm_audio_pack(*args, packed, index, n_open, hip.stream()))
+            drain._submit()
+            return None
+        t = self._torch
+        packed = hip.empty(tuple(audio.shape), t.int16 if pcm.format == hip.RCFM_PCM_S16 else t.float32)
+        index = hip.empty((count,), t.int32)
+        n_open = hip.empty((1,), t.int32)
+        hip.check(self._lib.rcfm_audio_pack(*args, hip.ptr(packed), hip.ptr(index), hip.ptr(n_open), hip.stream()))
+        if self._cuda and not numpy_output:
+            return index, packed, n_open
+        n = int(hip.to_host(n_open)[0])
+        return hip.to_host(index[:n]), hip.to_host(packed[:n])
+
     def _plan_uniform(self):
         """(kind, B, A, tau) -- plus the AGC setting where there is one -- when every channel of the tuner carries the
         same demodulator class and geometry, else None; cached per channel-list version."""

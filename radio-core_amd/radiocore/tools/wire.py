@@ -10,7 +10,7 @@ itself (pyzmq) stays outside the package.
 
 import numpy as np
 
-__all__ = ["frames", "parse_frame"]
+__all__ = ["frames", "frames_packed", "parse_frame"]
 
 
 def frames(channels, audio, open_mask=None):
@@ -27,9 +27,21 @@ def frames(channels, audio, open_mask=None):
     return [[ch.address_bytes, audio[i].tobytes()] for i, ch in enumerate(channels) if open_mask[i]]
 
 
-def parse_frame(message, audio_channels):
-    """(center frequency in Hz, float32 [A, audio_channels]) from one multipart message."""
+def frames_packed(channels, index, audio):
+    """[(address_bytes, payload_bytes)] for packed audio (Tuner.run_all_packed, Drain.next): row k of `audio`
+    [n_open, A, ch] belongs to channel index[k], and the payload is the row's bytes in its own dtype (int16 PCM, or float32).
+    Channels that are not listed produce no message."""
+    audio = np.asarray(audio)
+    index = np.asarray(index)
+    if audio.ndim != 3 or index.ndim != 1 or index.shape[0] != audio.shape[0]:
+        raise ValueError("audio must be [listed channels, samples, audio_channels] with one index per row")
+    return [[channels[int(c)].address_bytes, np.ascontiguousarray(audio[k]).tobytes()] for k, c in enumerate(index)]
+
+
+def parse_frame(message, audio_channels, dtype=np.float32):
+    """(center frequency in Hz, `dtype` [A, audio_channels]) from one multipart message (dtype: float32 as the reference
+    sends it, int16 for frames_packed of PCM audio)."""
     address, payload = message
     freq = int.from_bytes(address, byteorder="little")
-    pcm = np.frombuffer(payload, dtype=np.float32)
+    pcm = np.frombuffer(payload, dtype=dtype)
     return freq, pcm.reshape(-1, audio_channels)
