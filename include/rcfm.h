@@ -50,7 +50,9 @@ extern "C" {
                             that never calls rcfm_demod_set_agc launches what it launched before);
                             rcfm_tuner_load_raw and rcfm_iq_convert added (new symbols only; rcfm_tuner_load launches what it
                             launched before);
-                            rcfm_audio_pack and rcfm_drain_* added (new symbols only, nothing existing changed) */
+                            rcfm_audio_pack and rcfm_drain_* added (new symbols only, nothing existing changed);
+                            rcfm_tuner_iq_estimate, rcfm_tuner_iq_correct and rcfm_tuner_set_iq_balance added (new symbols
+                            only; a handle that never calls rcfm_tuner_set_iq_balance launches what it launched before) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -253,6 +255,51 @@ int rcfm_tuner_carriers(rcfm_tuner_t t, int first, int count, float gate, void* 
  * RCFM_ERR_STATE while a window storage is attached (rcfm_tuner_attach_window): its layout was computed from the old
  * rolls.  RCFM_ERR_INDEX for a bad range, RCFM_ERR_ARG for a NULL handle or NULL rolls with count > 0. */
 int rcfm_tuner_retune(rcfm_tuner_t t, int first, int count, const int64_t* roll_host, void* stream);
+/* ---- IQ balance: imbalance estimate and image rejection on the loaded spectrum (no reference counterpart) ------------
+ * A receiver whose I and Q paths differ in gain and phase delivers x' = mu x + nu conj(x): a station at +f puts an image of
+ * itself at -f (5 % gain and 3 degrees phase error: 29 dB down).  In the loaded spectrum X (n bins) that reads
+ * X'[k] = mu X[k] + nu conj(X[k']), with k' = (n - k) mod n the mirror of bin k.  Bin 0 is its own mirror; for even n, bin
+ * n/2 is too.  With beta = nu / conj(mu), Y[k] = X'[k] - beta conj(X'[k']) = (mu - |nu|^2 / conj(mu)) X[k] exactly.
+ *
+ * Estimate.  Over the mirror pairs m in [m_lo, m_hi], 1 <= m_lo <= m_hi <= floor((n - 1) / 2) -- the self-mirrored bins are
+ * never part of it, so a DC offset cannot bias it, and a host may calibrate on a region it trusts --
+ *   P    = sum_m X[m] X[n - m]                      (complex product, no conjugate)
+ *   Q    = sum_m (|X[m]|^2 + |X[n - m]|^2)
+ *   c    = 2 P / Q
+ *   beta = c / (1 + sqrt(1 - min(|c|^2, 1)))        (the exact inverse of c = 2 beta / (1 + |beta|^2))
+ * Every product and square is formed in float64 from the float32 parts and summed in float64 in a fixed order that depends
+ * on (n, m_lo, m_hi) alone; there are no floating-point atomics: bit-identical from run to run, from stream to stream, and
+ * whether one output is NULL or both are present.  The finish computes beta in float64 and rounds once to float32; Q = 0 or
+ * anything non-finite gives beta = 0.
+ *   sums: [3] float64 device = Re P, Im P, Q; beta: [2] float32 device; either may be NULL, not both.
+ * The estimate is blind: it takes what correlates between mirror bins for imbalance.  Two unmodulated carriers at exactly
+ * mirrored frequencies correlate too and corrupt a per-buffer estimate; the answer is a range without them, or a fixed beta.
+ * One beta for the whole band is a frequency-flat model of the receiver.
+ *
+ * Correct.  For every bin k, Y[k] = X[k] - beta conj(X[k']) in float32, beta [2] float32 read from DEVICE memory (what an
+ * estimate on the same stream has just written, for instance); the self-mirrored bins use themselves.  Then, for a notch
+ * half-width dc_notch = w >= 0, the bins of signed index |s| <= w - 1 are set to exact zero (w = 0: none; w = 1: bin 0, where
+ * the receiver's DC offset sits).  Y replaces X in the storage, both halos included (spectrum_layout above): every later
+ * rcfm_tuner_run, rcfm_pipeline_run, rcfm_tuner_levels, rcfm_tuner_power_spectrum, rcfm_tuner_carriers and
+ * rcfm_pipeline_subcarrier reads the clean band.  A handle without halos works too.
+ *
+ * set_iq_balance.  RCFM_IQ_BALANCE_OFF (the default): a load launches what it launched before.  _FIXED: every
+ * rcfm_tuner_load and rcfm_tuner_load_raw queues the correction with (beta_re, beta_im), kept in a device slot of the
+ * handle, and the notch behind its FFT on the load's stream.  _AUTO: the estimate over all pairs, its finish and the
+ * correction with that buffer's own beta (beta_re, beta_im are ignored).  No host synchronisation in either; nothing is
+ * carried from buffer to buffer.  The host must not have loads of this handle in flight while it changes the setting.
+ *
+ * Readiness of estimate and correct as rcfm_tuner_power_spectrum over the full span: RCFM_ERR_STATE before a load and
+ * whenever not every bin is held -- a sharded load, rcfm_tuner_adopt, an attached window; a plain load into the handle's own
+ * spectrum or into an attached one is fine.  A load of a handle with a balance mode set whose shard keeps a window only
+ * returns RCFM_ERR_STATE itself, before anything is launched.
+ * RCFM_ERR_ARG, checked before any device call: NULL handle, both outputs NULL, NULL beta, an empty or out-of-range
+ * [m_lo, m_hi] (this includes every n < 3, also for _AUTO), dc_notch negative or above n / 2, an unknown mode, a fixed
+ * beta that is not finite or has |beta| >= 1. */
+enum { RCFM_IQ_BALANCE_OFF = 0, RCFM_IQ_BALANCE_FIXED = 1, RCFM_IQ_BALANCE_AUTO = 2 };
+int rcfm_tuner_iq_estimate(rcfm_tuner_t t, int64_t m_lo, int64_t m_hi, void* sums, void* beta, void* stream);
+int rcfm_tuner_iq_correct(rcfm_tuner_t t, const void* beta, int64_t dc_notch, void* stream);
+int rcfm_tuner_set_iq_balance(rcfm_tuner_t t, int mode, float beta_re, float beta_im, int64_t dc_notch);
 int rcfm_tuner_destroy(rcfm_tuner_t t);
 
 /* ---- demodulators (radiocore/analog/{fm,mfm,wbfm}.py) --------------------- */

@@ -216,6 +216,11 @@ struct rcfm_tuner_s {
     rcfm::DeviceBuffer levels_part;   // rcfm_tuner_levels: float64 [count][segments] sums of channels split over workgroups
     rcfm::DeviceBuffer carriers_part; // rcfm_tuner_carriers: CarrierPart [count][segments] of channels split over workgroups
     rcfm::DeviceBuffer power_part_sum, power_part_max;   // rcfm_tuner_power_spectrum: float64 sums / float32 maxima [cells][segments]
+    // rcfm_tuner_set_iq_balance (iq_balance.hip): what every load queues behind its FFT.  The fixed beta and the one the
+    // auto mode estimates per buffer live in float32 [2] slots of their own; iq_part: float64 [segments][3] of an estimate
+    int iq_mode = RCFM_IQ_BALANCE_OFF;
+    int64_t iq_notch = 0;
+    rcfm::DeviceBuffer iq_beta_fixed, iq_beta_auto, iq_part;
     rcfm::DeviceBuffer X;          // [halo | n bins | halo]: the halos repeat the far ends, so a channel's bins
     int64_t halo = 0;              //   base + d, |d| <= B/2 + 1, need no wrap-around (fused_passes.h)
     float2* ext = nullptr;         // rcfm_tuner_attach_spectrum: caller-owned storage of the same layout instead of X
@@ -298,6 +303,10 @@ struct rcfm_tuner_s {
                   hipStream_t s);
     void retune(int first, int count, const int64_t* roll_host, hipStream_t s);
     void power_spectrum(int64_t s0, int64_t L, int64_t M, float* power, float* peak, hipStream_t s);
+    void require_whole(const char* caller) const;
+    void iq_estimate(int64_t m_lo, int64_t m_hi, double* sums, float* beta, hipStream_t s);
+    void iq_correct(const float* beta, int64_t notch, hipStream_t s);
+    void iq_after_load(hipStream_t s);
     void run(int first, int count, float2* out, hipStream_t s, float* theta = nullptr, int theta_pitch = 0,
              int narrow_mode = -1, bool envelope = false);
 };

@@ -369,6 +369,11 @@ static int tuner_load(rcfm_tuner_t t, int format, const void* x, void* stream) {
         ArenaScope scope(t->arena);
         RC_REQUIRE(!t->ext_window, RCFM_ERR_STATE,
                    "rcfm_tuner_load needs storage for the whole spectrum: a window is attached (rcfm_tuner_attach_window)");
+        RC_REQUIRE(t->iq_mode == RCFM_IQ_BALANCE_OFF ||
+                       !(t->forward_engine && (t->use_aligned() ? t->windowed_aligned : t->windowed)),
+                   RCFM_ERR_STATE,
+                   "a sharded load keeps a window of the spectrum, the IQ balance needs every bin and its mirror "
+                   "(rcfm_tuner_shard, rcfm_tuner_set_iq_balance)");
         {
             StageTimer tm(ST_TUNER_FFT, as_stream(stream));
             if (format != 0 && !t->raw_fused()) {   // no first pass to ride on: convert, then the complex64 load
@@ -409,6 +414,7 @@ static int tuner_load(rcfm_tuner_t t, int format, const void* x, void* stream) {
             const int64_t f0 = (al ? *t->forward_aligned : *t->forward_engine).row_length(), rows = t->n / f0;
             t->set_held((int64_t)w.lo * f0, (((int64_t)w.hi - w.lo + rows) % rows + 1) * f0);
         }
+        t->iq_after_load(as_stream(stream));   // rcfm_tuner_set_iq_balance; off (the default): nothing
     });
 }
 

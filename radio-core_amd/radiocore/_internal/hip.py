@@ -30,7 +30,9 @@ RCFM_OPT_SSB_DIRECT = 11
 RCFM_IQ_CS16, RCFM_IQ_CS8, RCFM_IQ_CU8 = 1, 2, 3                  # rcfm_tuner_load_raw, rcfm_iq_convert
 RCFM_PCM_F32, RCFM_PCM_S16 = 0, 1                                 # rcfm_audio_pack
 RCFM_PACK_SEGMENT = 4096           # elements of a row one workgroup of the pack kernel takes per sweep (csrc/egress_kernel.h, kPackSegment)
-RCFM_TUNER_OPT_NARROW_TILES, RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                                # rcfm_tuner_set_option
+RCFM_IQ_BALANCE_OFF, RCFM_IQ_BALANCE_FIXED, RCFM_IQ_BALANCE_AUTO = 0, 1, 2   # rcfm_tuner_set_iq_balance
+RCFM_IQ_SEG_PAIRS, RCFM_IQ_MAX_SEGS = 16384, 1024   # mirror pairs per workgroup of an estimate, and the most workgroups (csrc/iq_balance.h)
+RCFM_TUNER_OPT_NARROW_TILES, RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                              # rcfm_tuner_set_option
 
 _ERR_SIZE, _ERR_INDEX, _ERR_RUNTIME, _ERR_ARG, _ERR_STATE = -1, -2, -3, -4, -5
 
@@ -78,6 +80,9 @@ SIGNATURES = {
     "rcfm_tuner_power_spectrum": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "rcfm_tuner_carriers": [_vp, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp],
     "rcfm_tuner_retune": [_vp, _i, _i, ctypes.POINTER(_i64), _vp],
+    "rcfm_tuner_iq_estimate": [_vp, _i64, _i64, _vp, _vp, _vp],
+    "rcfm_tuner_iq_correct": [_vp, _vp, _i64, _vp],
+    "rcfm_tuner_set_iq_balance": [_vp, _i, ctypes.c_float, ctypes.c_float, _i64],
     "rcfm_tuner_destroy": [_vp],
     "rcfm_demod_create": [_i, _i, _i, _i, _dbl, _i, ctypes.POINTER(_vp)],
     "rcfm_demod_run": [_vp, _i, _i, _vp, _vp, _vp],

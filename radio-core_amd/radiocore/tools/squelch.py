@@ -4,6 +4,8 @@
 median power density over the channels is the noise floor.  A threshold a fixed number of dB above it, scaled by each
 channel's bandwidth, is what ``Tuner.set_squelch`` gates every later buffer with: calibrate occasionally, gate every
 buffer.  Host numpy only; under sharding every rank calls it on its own range and supplies its own thresholds.
+(A receiver with IQ imbalance puts the image of every strong station into the mirror channel and opens it: see
+``Tuner.set_iq_balance`` and ``radiocore.tools.iq.balance_from``, the same recipe for the balance -- calibrate first.)
 """
 
 import numpy as np

@@ -81,6 +81,8 @@ class Tuner(Injector):
         self._fine = None          # retune: None or int64 [len(channels())] bins each channel was moved up (a new object per retune)
         self._handle_fine = None   # the _fine the device handle's rolls were last set from
         self._taps = {}            # (B, R, f, taps) -> (channels it holds, batched subcarrier handle) of subcarrier()
+        self._iq_balance = None    # set_iq_balance: None (off) or (mode, beta, dc_notch) (a new object per setting)
+        self._handle_iq = None     # the _iq_balance the device handle was last set to
 
     @property
     def input_frequency(self) -> float:
@@ -165,8 +167,11 @@ class Tuner(Injector):
             self._handle_key = key
             self._handle_fine = self._fine
             self._loaded_size = None
+            self._handle_iq = None
             if self._shard is not None:
                 hip.check(self._lib.rcfm_tuner_shard(h, self._shard[0], self._shard[1]))
+            if self._iq_balance is not None:
+                self._apply_iq_balance(h)
         return self._handle.value
 
     def _rolls(self, fine):
@@ -215,6 +220,8 @@ class Tuner(Injector):
         h = self._device_tuner(n)
         if self._handle_fine is not self._fine:        # a lane that follows the base tuner's retune, on its own stream
             self._apply_fine(h, self._fine)
+        if self._handle_iq is not self._iq_balance:    # ... and its set_iq_balance
+            self._apply_iq_balance(h)
         if whole and self._shard is not None:
             hip.check(self._lib.rcfm_tuner_shard(h, 0, len(self._bounds)))
             try:
@@ -422,6 +429,69 @@ class Tuner(Injector):
                                                       hip.stream()))
         out = [self._result(o, self._cuda and not numpy_output) for o in out]
         return (out[0], out[1]) if peak else out[0]
+
+    # ---- IQ balance (rcfm_tuner_iq_estimate / _iq_correct / _set_iq_balance; no reference counterpart) -----------------
+
+    def iq_imbalance(self, f_lo=None, f_hi=None, numpy_output: bool = True):
+        """How far the receiver's I and Q paths are apart, read from the loaded buffer: ``(beta, sums)``.  A mismatch in
+        gain and phase puts an image of every station at the mirrored frequency; ``beta`` (complex) is what
+        ``set_iq_balance(beta)`` removes it with, ``sums`` (float64 [3]: Re P, Im P, Q) is what ``iq.balance_from``
+        combines over several buffers.  ``f_lo`` / ``f_hi``: Hz above the input frequency, half-open like the span of
+        ``power_spectrum`` -- the estimate uses the bins in that range together with their mirror images (None: from the
+        first bin above the input frequency / up to the band's end).  The estimate is blind: two unmodulated carriers at
+        exactly mirrored frequencies look like imbalance, so restrict it to a range the host trusts.  Valid after a plain
+        ``load``; RuntimeError under ``shard``, after ``adopt`` or with a window attached (the mirror bins are elsewhere).
+        On a ``cuda=True`` tuner ``numpy_output=False`` returns the device tensors (float32 [2], float64 [3]) unsynchronised."""
+        if self._loaded_size is None:
+            raise RuntimeError("Tuner.iq_imbalance called before Tuner.load")
+        m_lo, m_hi = iq.pair_range(self._loaded_size, f_lo, f_hi)
+        handle = self._ready()
+        beta = hip.empty((2,), self._torch.float32)
+        sums = hip.empty((3,), self._torch.float64)
+        hip.check(self._lib.rcfm_tuner_iq_estimate(handle, m_lo, m_hi, hip.ptr(sums), hip.ptr(beta), hip.stream()))
+        if self._cuda and not numpy_output:
+            return beta, sums
+        b = hip.to_host(beta)
+        return complex(float(b[0]), float(b[1])), hip.to_host(sums)
+
+    def set_iq_balance(self, balance=None, dc_notch: int = 0):
+        """Image rejection on every buffer from now on: ``load`` / ``load_raw`` (and ``Lanes.submit``) queue the
+        correction ``X[k] -= beta conj(X[-k])`` of the spectrum behind their FFT, on the device and on the caller's stream,
+        and ``run`` / ``run_all`` / ``levels`` / squelch / ``power_spectrum`` / ``carriers`` / ``subcarrier`` see the clean
+        band.  ``balance``: ``"auto"`` estimates beta blindly from each buffer itself; a complex number is a fixed beta
+        (from ``iq_imbalance`` or ``iq.balance_from``: calibrate occasionally); ``None`` (the default) turns it off: nothing
+        more is launched than before.  ``dc_notch = w`` zeroes the 2 w - 1 bins around the input frequency, where the
+        receiver's DC offset sits (0: none).  ValueError for another string, a beta that is not finite or not below 1 in
+        magnitude, a negative notch or one beyond half the band.  Needs the whole spectrum: ``load`` raises RuntimeError
+        on a sharded tuner."""
+        dc_notch = int(dc_notch)
+        if dc_notch < 0:
+            raise ValueError("dc_notch must be >= 0")
+        if self._input_bandwidth and dc_notch > int(self._input_bandwidth) // 2:
+            raise ValueError("dc_notch reaches beyond half the band")
+        if balance is None:
+            setting = None
+        elif isinstance(balance, str):
+            if balance != "auto":
+                raise ValueError('set_iq_balance: None, "auto" or a complex beta, not %r' % (balance,))
+            setting = (hip.RCFM_IQ_BALANCE_AUTO, 0j, dc_notch)
+        else:
+            try:
+                beta = complex(balance)
+            except (TypeError, ValueError):
+                raise ValueError('set_iq_balance: None, "auto" or a complex beta, not %r' % (balance,))
+            beta = complex(np.float32(beta.real), np.float32(beta.imag))     # what the device slot will hold
+            if not (np.isfinite(beta.real) and np.isfinite(beta.imag)) or abs(beta) >= 1.0:
+                raise ValueError("a fixed beta must be finite and below 1 in magnitude")
+            setting = (hip.RCFM_IQ_BALANCE_FIXED, beta, dc_notch)
+        self._iq_balance = setting
+        if self._handle is not None and self._handle_key[1] == self._version:
+            self._apply_iq_balance(self._handle.value)
+
+    def _apply_iq_balance(self, handle):
+        mode, beta, notch = self._iq_balance if self._iq_balance is not None else (hip.RCFM_IQ_BALANCE_OFF, 0j, 0)
+        hip.check(self._lib.rcfm_tuner_set_iq_balance(handle, mode, beta.real, beta.imag, notch))
+        self._handle_iq = self._iq_balance
 
     def set_squelch(self, threshold=None):
         """Mute what is below a level: from now on ``run_all`` / ``run_each`` (and ``Lanes.submit``) compare every
@@ -719,6 +789,7 @@ class Tuner(Injector):
     def _sync_lane(self, base):
         if self._squelch is not base._squelch:             # the base's squelch setting (a new object per set_squelch)
             self._squelch, self._squelch_dev, self._open = base._squelch, None, None
+        self._iq_balance = base._iq_balance                # ... its IQ balance (the next load applies it; per buffer, nothing to fence)
         if self._fine is not base._fine:                   # ... and its fine-tune (a new object per retune): the next load applies it
             self._fine, self._abi_arrays = base._fine, None
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
