@@ -52,7 +52,9 @@ extern "C" {
                             launched before);
                             rcfm_audio_pack and rcfm_drain_* added (new symbols only, nothing existing changed);
                             rcfm_tuner_iq_estimate, rcfm_tuner_iq_correct and rcfm_tuner_set_iq_balance added (new symbols
-                            only; a handle that never calls rcfm_tuner_set_iq_balance launches what it launched before) */
+                            only; a handle that never calls rcfm_tuner_set_iq_balance launches what it launched before);
+                            rcfm_tone_bank_* and rcfm_tone_score added (new symbols only, nothing existing changed; a frame
+                            length above 2^24 is refused: an implementation limit, the definition itself has none) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -88,6 +90,7 @@ typedef enum rcfm_demod_kind {
 typedef struct rcfm_tuner_s* rcfm_tuner_t;
 typedef struct rcfm_demod_s* rcfm_demod_t;
 typedef struct rcfm_subcarrier_s* rcfm_subcarrier_t;
+typedef struct rcfm_tone_bank_s* rcfm_tone_bank_t;
 typedef struct rcfm_resampler_s* rcfm_resampler_t;
 typedef struct rcfm_feeder_s* rcfm_feeder_t;
 typedef struct rcfm_comm_s* rcfm_comm_t;
@@ -473,6 +476,66 @@ int rcfm_subcarrier_destroy(rcfm_subcarrier_t h);
 enum { RCFM_PCM_F32 = 0, RCFM_PCM_S16 = 1 };
 int rcfm_audio_pack(const void* audio, const void* open, int count, size_t row, int format, float gain,
                     void* packed, void* index, void* n_open, void* stream);
+
+/* ---- tone bank: CTCSS / SELCAL detection and tone squelch on the audio (no reference counterpart) -------------------------
+ * The signalling tones a receiver of these bands is expected to understand: the CTCSS tone (67 .. 254 Hz) that separates the
+ * users of one narrow-FM channel, the two tone pairs of an aeronautical SELCAL call.  After rcfm_pipeline_run the audio
+ * [C][A][ch] lies on the device; the tone bank gives, per channel and time frame, the power at each of K given frequencies
+ * and the frame's total power, for FM, AM and SSB audio alike.
+ *
+ * Definition.  One channel's audio is x[0..A), float32, read from audio[c][i step + offset] with step in {1, 2} and
+ * 0 <= offset < step (a row holds A step floats: step = 2 addresses one side of WBFM's interleaved stereo).  A bank has
+ *   K        tones, 1 <= K <= 64;
+ *   nu[k]    double, cycles per sample, finite, 0 <= nu[k] <= 0.5;
+ *   L        a frame length, 1 <= L (this library: L <= 2^24, so that the coarse table below, K ceil(L / 16) complex64 built
+ *            on the host, stays below 512 MiB; the definition has no upper limit and nothing else depends on this one);
+ *   w[0..L)  an optional real window, float32, every element finite, S = sum w[i] (taken in float64) > 0; NULL: w = 1.
+ * F = floor(A / L) frames; a tail of A mod L samples is not read; A < L is RCFM_ERR_SIZE at run.
+ *   Z[c][f][k] = (1/S) sum_{i=0}^{L-1} w[i] x_c[f L + i] exp(-2 pi j frac(nu[k] i))      (the phase is frame-local)
+ *   P[c][f][k] = |Z[c][f][k]|^2               float32 [count][F][K]
+ *   E[c][f]    = (1/L) sum_i x_c[f L + i]^2   float32 [count][F]     (no window)
+ * A sinusoid of amplitude a exactly at nu[k] gives P ~ a^2 / 4 for any window; P / E is the share of the frame's power at
+ * the tone, and detection is thresholded on that ratio.
+ * Evaluation form.  exp(-2 pi j frac(nu (16 m + j))) = coarse[k][m] fine[k][j], j = 0 .. 15: both tables are computed on the
+ * host with frac(nu i) in float64 and stored as complex64; per 16 samples and tone the device forms
+ * sum_j (x w)[16 m + j] fine[k][j] with float32 FMAs and multiplies it by coarse[k][m].  No recurrence runs over a frame and
+ * no sine or cosine is evaluated on the device.  |Z|^2 / S^2 is formed in float64 from the float32 sums and rounded once;
+ * the energy is summed in float64 and rounded once.
+ * Determinism.  No atomics.  Every sum has one order, a function of (L, K) alone: bit-identical from run to run, from stream
+ * to stream, for a sub-range of channels against the whole range, and whether energy is NULL or not.  (A frame longer than
+ * 8192 samples is split over ceil(L / 8192) workgroups whose float sums a finish step adds in segment order; they pass
+ * through a buffer the handle keeps per stream.)
+ * Such a bank (L > 8192 only) is asynchronous from its second run on a stream on: the first run on a stream, and a later one
+ * with more channels than any before it on that stream (up to 65 535 are sized for), allocates that buffer with hipMalloc --
+ * growth frees the old one first, which waits for the device -- so do not make that run inside a stream capture; warm the
+ * bank up with the largest count first.  The buffers, count F ceil(L / 8192) (8 K' + 8) bytes each with K' = K rounded up
+ * to a multiple of 8, are kept per stream handle until rcfm_tone_bank_destroy: a host that keeps creating and destroying
+ * streams should run its banks of long frames on streams it keeps.  Banks with L <= 8192 own no such buffer and never allocate
+ * in run.
+ *
+ * create   nu_host [K], window_host [L] or NULL.  RCFM_ERR_ARG before any device call: a NULL pointer, K outside 1 .. 64,
+ *          L outside 1 .. 2^24, a nu that is not finite or outside [0, 0.5], a window element that is not finite, S <= 0.
+ * run      audio [count][A step] float32 -> power [count][F][K], energy [count][F] (may be NULL), asynchronously on `stream`.
+ *          RCFM_ERR_ARG before any device call: a NULL handle, audio or power, count < 1, A < 1, step outside {1, 2}, offset
+ *          outside [0, step), a pointer not aligned for a float.  RCFM_ERR_SIZE: A < L.
+ *
+ * Tone squelch.  rcfm_tone_score computes, for each channel c of power [count][F][K] and energy [count][F]:
+ *   score[c] = max_f P[c][f][want[c]] / E[c][f]      frames with E == 0 contribute 0, a NaN ratio never wins
+ *   want[c] == -1          score[c] = +inf: no tone is required
+ *   gate[c] == 0           score[c] = NaN, whatever want[c] is (gate: [count] uint8, the open mask of a level squelch, or NULL)
+ * score then goes through rcfm_squelch(score, ratio_threshold, ...), which opens on score >= threshold and is false for NaN:
+ * the zero fill, the open mask, rcfm_audio_pack and the drain work unchanged, and a level squelch and a tone squelch combine
+ * through gate.  want is an int32 [count] DEVICE array, so it cannot be validated before the launch: a host checks its range
+ * (radiocore's Tuner.set_tones does), and the kernel defines the rest -- a want[c] outside [-1, K) reads no memory and gives
+ * NaN, a channel that never opens.
+ *          RCFM_ERR_ARG before any device call: NULL power, energy, want or score, count < 1, F < 1, K outside 1 .. 64, a
+ *          pointer not aligned for its element. */
+int rcfm_tone_bank_create(int K, const double* nu_host, int L, const float* window_host, rcfm_tone_bank_t* out);
+int rcfm_tone_bank_run(rcfm_tone_bank_t b, const void* audio, int count, int A, int step, int offset, void* power, void* energy,
+                       void* stream);
+int rcfm_tone_bank_destroy(rcfm_tone_bank_t b);
+int rcfm_tone_score(const void* power, const void* energy, const void* want, const void* gate, int count, int F, int K,
+                    void* score, void* stream);
 
 /* ---- host ingest (the step before Tuner.load) -------------------------------- */
 

@@ -32,6 +32,7 @@ RCFM_PCM_F32, RCFM_PCM_S16 = 0, 1                                 # rcfm_audio_p
 RCFM_PACK_SEGMENT = 4096           # elements of a row one workgroup of the pack kernel takes per sweep (csrc/egress_kernel.h, kPackSegment)
 RCFM_IQ_BALANCE_OFF, RCFM_IQ_BALANCE_FIXED, RCFM_IQ_BALANCE_AUTO = 0, 1, 2   # rcfm_tuner_set_iq_balance
 RCFM_IQ_SEG_PAIRS, RCFM_IQ_MAX_SEGS = 16384, 1024   # mirror pairs per workgroup of an estimate, and the most workgroups (csrc/iq_balance.h)
+RCFM_TONE_MAX_K, RCFM_TONE_SEGMENT = 64, 8192    # tones of a bank; samples of a frame per workgroup (csrc/tones.h)
 RCFM_TUNER_OPT_NARROW_TILES, RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                              # rcfm_tuner_set_option
 
 _ERR_SIZE, _ERR_INDEX, _ERR_RUNTIME, _ERR_ARG, _ERR_STATE = -1, -2, -3, -4, -5
@@ -111,6 +112,10 @@ SIGNATURES = {
     "rcfm_feeder_copied": [_vp, ctypes.POINTER(ctypes.c_uint64)],
     "rcfm_feeder_destroy": [_vp],
     "rcfm_audio_pack": [_vp, _vp, _i, _sz, _i, ctypes.c_float, _vp, _vp, _vp, _vp],
+    "rcfm_tone_bank_create": [_i, ctypes.POINTER(_dbl), _i, _fp, ctypes.POINTER(_vp)],
+    "rcfm_tone_bank_run": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "rcfm_tone_bank_destroy": [_vp],
+    "rcfm_tone_score": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
     "rcfm_drain_create": [_sz, _i, _i, ctypes.POINTER(_vp)],
     "rcfm_drain_begin": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)],
     "rcfm_drain_submit": [_vp, _vp],

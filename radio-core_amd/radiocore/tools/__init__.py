@@ -14,4 +14,5 @@ from radiocore.tools.feeder import *
 from radiocore.tools.egress import *
 from radiocore.tools.lanes import *
 from radiocore.tools.arena import *
-from radiocore.tools import iq, rds
+from radiocore.tools.tonebank import *
+from radiocore.tools import iq, rds, tones

@@ -44,7 +44,7 @@ class Lanes:
         self._streams = [self._torch.cuda.Stream() for _ in range(depth)]
         self._next = 0
         self._pending = {}          # ticket -> (end event, audio tensor, event behind the load = last reader of the input,
-                                    #            the squelch's device masks or None)
+                                    #            the squelch's device masks or None, the tone bank's device (P, E) or None)
         self._spans = {}            # timing=True: ticket -> (start event, end event)
 
     @property
@@ -55,7 +55,8 @@ class Lanes:
         """Queue Tuner.load + Tuner.run_all of one buffer on the next lane; returns a ticket for ``result``.
         each=True: Tuner.run_each instead (channels of different classes and geometries; ``result`` then returns its
         list of per-channel arrays).  With ``tuner.set_squelch`` set, the lane queues the levels and the squelch behind
-        its demodulators like ``run_all`` does; ``result(ticket, open_mask=True)`` returns the buffer's mask.
+        its demodulators like ``run_all`` does; ``result(ticket, open_mask=True)`` returns the buffer's mask.  The same
+        holds for ``tuner.set_tones``: ``result(ticket, tones=True)`` returns the buffer's tone powers.
         raw=True: ``input_signal`` holds interleaved integer I, Q and the lane loads it with Tuner.load_raw."""
         ticket = self._next
         self._next += 1
@@ -75,7 +76,7 @@ class Lanes:
             loaded = self._event(st)            # the wideband FFT is the LAST reader of the input buffer
             audio = t._run_each_device() if each else t._run_all_device(chunk)
             ev = self._event(st)
-        self._pending[ticket] = (ev, audio, loaded, t._open)
+        self._pending[ticket] = (ev, audio, loaded, t._open, t._tone_out)
         if self._timing:
             self._spans[ticket] = (start, ev)
         return ticket
@@ -93,11 +94,12 @@ class Lanes:
         _, end = self._spans[earlier]
         return float(start.elapsed_time(end))
 
-    def result(self, ticket: int, numpy_output: bool = True, open_mask: bool = False):
+    def result(self, ticket: int, numpy_output: bool = True, open_mask: bool = False, tones: bool = False):
         """The audio of one submitted buffer, [C, A, ch] float32 (the shard's block after Tuner.shard).
         open_mask=True: ``(audio, mask)`` with the squelch's numpy bool [C] of that buffer (Tuner.open_mask; None when
-        the buffer was submitted with squelch off)."""
-        ev, audio, _, masks = self._pending.pop(ticket)
+        the buffer was submitted with squelch off).  tones=True: the tone bank's ``(P, E)`` of that buffer
+        (Tuner.tone_power; None when it was submitted without a bank) comes last in the tuple."""
+        ev, audio, _, masks, tone_out = self._pending.pop(ticket)
         device_output = self._base._cuda and not numpy_output
         if device_output:
             cur = self._torch.cuda.current_stream()
@@ -110,9 +112,16 @@ class Lanes:
             out = self._base._each_result(audio, device_output)
         else:
             out = audio if device_output else hip.to_host(audio)
-        if not open_mask:
-            return out
-        return out, (Tuner._mask_result(masks) if masks is not None else None)
+        extra = []
+        if open_mask:
+            extra.append(Tuner._mask_result(masks) if masks is not None else None)
+        if tones:
+            if device_output and tone_out is not None:
+                for p, e in tone_out:
+                    p.record_stream(cur)
+                    e.record_stream(cur)
+            extra.append(self._base._tone_result(tone_out, device_output) if tone_out is not None else None)
+        return (out, *extra) if extra else out
 
     def hold_current_stream(self, ticket: int):
         """Order the CURRENT stream behind the last READ of one submitted buffer's input (the wideband FFT of

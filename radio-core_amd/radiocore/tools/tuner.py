@@ -83,6 +83,10 @@ class Tuner(Injector):
         self._taps = {}            # (B, R, f, taps) -> (channels it holds, batched subcarrier handle) of subcarrier()
         self._iq_balance = None    # set_iq_balance: None (off) or (mode, beta, dc_notch) (a new object per setting)
         self._handle_iq = None     # the _iq_balance the device handle was last set to
+        self._tones = None         # set_tones: None (off) or (bank, want int32 [C] or None, ratio float32 [C] or None) (a new object per setting)
+        self._tones_dev = None     # (channel-list version, device int32 [C], device float32 [C]) of a tone squelch
+        self._tone_out = None      # device (P, E) of the last run_all / run_each, one pair per launch group
+        self._tones_ready = None   # (launch-plan key, the _tones it was checked for): the bank fits every group's audio length
 
     @property
     def input_frequency(self) -> float:
@@ -512,7 +516,8 @@ class Tuner(Injector):
         self._open = None
 
     def open_mask(self):
-        """numpy bool [count]: which channels the squelch left open in this tuner's last ``run_all`` / ``run_each``."""
+        """numpy bool [count]: which channels the squelch -- the level squelch, the tone squelch, or both combined -- left
+        open in this tuner's last ``run_all`` / ``run_each``."""
         if self._open is None:
             raise RuntimeError("open_mask: no run_all / run_each with squelch set (set_squelch) yet")
         return self._mask_result(self._open)
@@ -530,6 +535,109 @@ class Tuner(Injector):
             full = np.ascontiguousarray(np.broadcast_to(a, (len(self._bounds),)))
             self._squelch_dev = (self._version, hip.to_device(full, self._torch.float32))
         return self._squelch_dev[1]
+
+    # ---- tone bank and tone squelch (rcfm_tone_bank_run / rcfm_tone_score; no reference counterpart) ---------------------
+
+    def set_tones(self, bank=None, want=None, ratio=None):
+        """Signalling tones on the audio: with a ``radiocore.ToneBank``, ``run_all`` / ``run_each`` / ``run_all_packed`` (and
+        ``Lanes.submit``) queue the bank behind the demodulators of each group, on the caller's stream and without a host
+        synchronisation, and ``tone_power()`` returns what it measured: per channel and frame the power at each of the
+        bank's tones and the frame's total power.  It runs before the level squelch, on the left side of WBFM's stereo.
+        With ``want`` and ``ratio`` it is a tone squelch as well: a channel stays open only when, in some frame, the share
+        ``P / E`` of its wanted tone reaches its ratio -- and when the level squelch, if one is set, leaves it open;
+        everything else comes back as exact zeros and ``open_mask()`` returns the combined mask.  ``want``: one entry per
+        channel or one for all, a tone index (int), a frequency of the bank in Hz (float), or None / -1 for "no tone
+        needed"; ``ratio``: a scalar or one per channel.  ``None`` (the default) turns it all off: nothing more is launched
+        than before.  ValueError, here or -- for channels added later -- in the next run before anything of it is launched,
+        for a bank that does not fit a channel's audio: a frame longer than the audio, a tone above half its rate, a window
+        of another length or without a positive sum; the setting in force stays."""
+        C = len(self._bounds)
+        if bank is None:
+            if want is not None or ratio is not None:
+                raise ValueError("set_tones: want and ratio need a bank")
+            self._tones = None
+        else:
+            if (want is None) != (ratio is None):
+                raise ValueError("set_tones: a tone squelch takes both want and ratio")
+            w = r = None
+            if ratio is not None:
+                if isinstance(want, (list, tuple, np.ndarray)):
+                    if len(want) != C:
+                        raise ValueError("wanted tones: one for all or one per channel (%d)" % C)
+                    w = np.array([bank.index(v.item() if isinstance(v, np.generic) else v) for v in want], dtype=np.int32)
+                else:
+                    w = np.full(C, bank.index(want), dtype=np.int32)
+                r = np.array(ratio, dtype=np.float32)
+                if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != C):
+                    raise ValueError("tone ratios: a scalar or one per channel (%d)" % C)
+                r = np.array(np.broadcast_to(r, (C,)))           # (a copy: writable, contiguous)
+            setting = (bank, w, r)
+            self._fit_tones(setting)               # refused here, with the old setting still in force
+            self._tones = setting
+        self._tones_dev = None
+        self._tone_out = None
+        self._open = None
+
+    def _fit_tones(self, setting):
+        """The bank's device handle for the audio length of every group of the launch plan, made now: whatever is wrong
+        with the bank for these channels raises here, before a run has advanced any demodulator state.  Once per
+        (channel list, shard, setting)."""
+        if not self._bounds:
+            return
+        groups, first, count = self._launch_plan()
+        key = (self._plan[0], setting)
+        if self._tones_ready is not None and self._tones_ready[0] == key[0] and self._tones_ready[1] is setting:
+            return
+        for A in sorted({g[4] for g in groups if g[2] is not None}):
+            setting[0]._handle(A)
+        self._tones_ready = key
+
+    def tone_power(self, numpy_output: bool = True):
+        """``(P [count, F, K], E [count, F])`` of this tuner's last ``run_all`` / ``run_each`` with a tone bank set: the
+        power at each tone and the total power of every frame of every channel.  (``run_each`` over groups whose audio
+        lengths give different frame counts: a list with one such pair per group.)"""
+        if self._tone_out is None:
+            raise RuntimeError("tone_power: no run_all / run_each with a tone bank set (set_tones) yet")
+        return self._tone_result(self._tone_out, self._cuda and not numpy_output)
+
+    def _tone_result(self, pairs, device_output):
+        t = self._torch
+        if len({tuple(p.shape[1:]) for p, _ in pairs}) > 1:
+            return [(self._result(p, device_output), self._result(e, device_output)) for p, e in pairs]
+        P = pairs[0][0] if len(pairs) == 1 else t.cat([p for p, _ in pairs])
+        E = pairs[0][1] if len(pairs) == 1 else t.cat([e for _, e in pairs])
+        return self._result(P, device_output), self._result(E, device_output)
+
+    def _tone_squelch(self, first, count, audio, tones, gate):
+        # behind the group's tone bank (and level squelch): the wanted tone's best share, then mask + zero fill on it
+        bank, want, ratio = self._tones
+        if self._tones_dev is None or self._tones_dev[0] != self._version:
+            if want.shape[0] != len(self._bounds):
+                raise ValueError("wanted tones were set for %d channels, the tuner has %d" % (want.shape[0], len(self._bounds)))
+            self._tones_dev = (self._version, hip.to_device(want, self._torch.int32), hip.to_device(ratio, self._torch.float32))
+        _, want_dev, ratio_dev = self._tones_dev
+        P, E = tones
+        score = hip.empty((count,), self._torch.float32)
+        mask = hip.empty((count,), self._torch.uint8)
+        s = hip.stream()
+        hip.check(self._lib.rcfm_tone_score(hip.ptr(P), hip.ptr(E), ctypes.c_void_p(want_dev.data_ptr() + 4 * first),
+                                            hip.ptr(gate) if gate is not None else None, count, int(P.shape[1]),
+                                            int(P.shape[2]), hip.ptr(score), s))
+        hip.check(self._lib.rcfm_squelch(hip.ptr(score), ctypes.c_void_p(ratio_dev.data_ptr() + 4 * first), count,
+                                         audio.numel() // count, hip.ptr(audio), hip.ptr(mask), s))
+        return mask
+
+    def _gates(self, handle, first, count, audio):
+        """What follows a group's rcfm_pipeline_run on the same stream: the tone bank, the level squelch, the tone squelch,
+        each only when set.  (tones (P, E) or None, open mask or None)."""
+        tones = mask = None
+        if self._tones is not None:
+            tones = self._tones[0].run(audio, step=int(audio.shape[2]), offset=0)
+        if self._squelch is not None:
+            mask = self._squelch_group(handle, first, count, audio)
+        if tones is not None and self._tones[1] is not None:
+            mask = self._tone_squelch(first, count, audio, tones, mask)
+        return tones, mask
 
     def _squelch_group(self, handle, first, count, audio):
         # behind the group's rcfm_pipeline_run on the same stream: levels of its channels, then mask + zero fill
@@ -587,10 +695,14 @@ class Tuner(Injector):
             raise ValueError("run_all needs one demodulator class and geometry for all channels")
         kind, B, A, tau = geo[:4]
         ch = 2 if kind == hip.RCFM_WBFM else 1
+        if self._tones is not None:
+            self._fit_tones(self._tones)
         audio = hip.empty((count, A, ch), self._torch.float32)
         hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk, *geo[4:]), first, count,
                                               hip.ptr(audio), hip.stream()))
-        self._open = [self._squelch_group(handle, first, count, audio)] if self._squelch is not None and count else None
+        tones, mask = self._gates(handle, first, count, audio) if count else (None, None)
+        self._open = [mask] if mask is not None else None
+        self._tone_out = [tones] if tones is not None else None
         return audio
 
     def run_all_packed(self, pcm, numpy_output: bool = True, chunk: int = 0, drain=None):
@@ -661,7 +773,10 @@ class Tuner(Injector):
         handle = self._ready()
         groups, first, count = self._launch_plan()
         blocks = []
-        masks = [] if self._squelch is not None else None
+        masks = [] if self._squelch is not None or (self._tones is not None and self._tones[1] is not None) else None
+        tone_out = [] if self._tones is not None else None
+        if self._tones is not None:
+            self._fit_tones(self._tones)
         for i, n, kind, B, A, tau, *agc in groups:
             if kind is None:
                 raise ValueError("run_each needs an FM, MFM, WBFM, AM, USB or LSB demodulator on every channel")
@@ -669,10 +784,14 @@ class Tuner(Injector):
             audio = hip.empty((n, A, ch), self._torch.float32)
             hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, 0, *agc), i, n,
                                                   hip.ptr(audio), hip.stream()))
+            tones, mask = self._gates(handle, i, n, audio)
             if masks is not None:
-                masks.append(self._squelch_group(handle, i, n, audio))
+                masks.append(mask)
+            if tone_out is not None:
+                tone_out.append(tones)
             blocks.append((n, ch, audio))
         self._open = masks
+        self._tone_out = tone_out
         return blocks
 
     def _each_result(self, blocks, device_output):
@@ -789,6 +908,8 @@ class Tuner(Injector):
     def _sync_lane(self, base):
         if self._squelch is not base._squelch:             # the base's squelch setting (a new object per set_squelch)
             self._squelch, self._squelch_dev, self._open = base._squelch, None, None
+        if self._tones is not base._tones:                 # ... its tone bank and tone squelch (a new object per set_tones)
+            self._tones, self._tones_dev, self._tone_out, self._open, self._tones_ready = base._tones, None, None, None, None
         self._iq_balance = base._iq_balance                # ... its IQ balance (the next load applies it; per buffer, nothing to fence)
         if self._fine is not base._fine:                   # ... and its fine-tune (a new object per retune): the next load applies it
             self._fine, self._abi_arrays = base._fine, None
