@@ -54,7 +54,8 @@ extern "C" {
                             rcfm_tuner_iq_estimate, rcfm_tuner_iq_correct and rcfm_tuner_set_iq_balance added (new symbols
                             only; a handle that never calls rcfm_tuner_set_iq_balance launches what it launched before);
                             rcfm_tone_bank_* and rcfm_tone_score added (new symbols only, nothing existing changed; a frame
-                            length above 2^24 is refused: an implementation limit, the definition itself has none) */
+                            length above 2^24 is refused: an implementation limit, the definition itself has none);
+                            rcfm_audio_filter_* added (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -91,6 +92,7 @@ typedef struct rcfm_tuner_s* rcfm_tuner_t;
 typedef struct rcfm_demod_s* rcfm_demod_t;
 typedef struct rcfm_subcarrier_s* rcfm_subcarrier_t;
 typedef struct rcfm_tone_bank_s* rcfm_tone_bank_t;
+typedef struct rcfm_audio_filter_s* rcfm_audio_filter_t;
 typedef struct rcfm_resampler_s* rcfm_resampler_t;
 typedef struct rcfm_feeder_s* rcfm_feeder_t;
 typedef struct rcfm_comm_s* rcfm_comm_t;
@@ -536,6 +538,59 @@ int rcfm_tone_bank_run(rcfm_tone_bank_t b, const void* audio, int count, int A, 
 int rcfm_tone_bank_destroy(rcfm_tone_bank_t b);
 int rcfm_tone_score(const void* power, const void* energy, const void* want, const void* gate, int count, int F, int K,
                     void* score, void* stream);
+
+/* ---- audio filter: biquad sections per channel, carried across buffers (no reference counterpart) -------------------------
+ * What a receiver applies to a narrow-band channel's audio before its speaker: the 300 Hz high-pass that strips the CTCSS
+ * tone, narrow FM's de-emphasis, the voice band-pass of an airband set.  Such filters are recursive: a few second-order
+ * sections where an FIR of the same slope needs hundreds to thousands of taps.
+ *
+ * Definition.  A filter is S sections, 1 <= S <= 8; section s is b0 b1 b2 a0 a1 a2 in float64, the row layout of scipy's
+ * `sos`.  a0 must be exactly 1, every coefficient finite, every section strictly stable: |a2| < 1 and |a1| < 1 + a2.
+ * One row is x[0..n), float32.  Section s maps its input u to its output y in transposed direct form II, the form of
+ * scipy.signal.sosfilt:
+ *   y[i] = b0 u[i] + z0
+ *   z0'  = b1 u[i] - a1 y[i] + z1
+ *   z1'  = b2 u[i] - a2 y[i]
+ * Section s + 1 reads section s's output; the last section's output is rounded once to float32.  All of the recurrence's
+ * arithmetic -- runs, aggregates, scan, carries, state -- is float64: a float32 recurrence is off by 1e-5 .. 6e-5 of the
+ * row's peak for the voice filters at 48 kHz, this form by 5e-8.
+ * State.  (z0, z1) per channel, per leg and per section, float64 [C][ch][S][2], carried from call to call: filtering a row
+ * of 2 n samples equals two calls of n, up to rounding.  It is all zeros after create and after reset: these are sosfilt's
+ * zero initial conditions (a filter at rest), NOT scipy.signal.sosfilt_zi's steady state of a step -- a row with a DC level
+ * starts with the filter's step response.  The library does not inspect the data: a NaN or infinity in a row stays in that
+ * row's state until a reset.
+ * Layout.  The audio is [count][n][ch], ch in {1, 2}; with ch = 2 the row is WBFM's interleaved stereo, and each leg is a
+ * row of its own with its own state.
+ * Evaluation form.  One workgroup per channel; the row passes through on-chip memory in segments of 8192 floats, read once
+ * and written once whatever S is.  Thread t owns a run of R = 33 samples.  Per section: the recurrence over the run from
+ * zero state gives the run's end state v_t; the state entering run t follows s_t = M^R s_(t-1) + v_(t-1) with
+ * M = [[-a1, 1], [-a2, 0]], an affine scan with host-built float64 tables M^(R 2^k), k = 0 .. 5, and M^(64 R); the run is
+ * then repeated from s_t.  The tables only decay, since sections are stable.
+ * Determinism.  No atomics; the order of every operation is a function of (n, ch, S) alone: bit-identical from run to run,
+ * from stream to stream, for a sub-range of channels against the whole range, in place against out of place, whatever the
+ * alignment of the rows, and with select NULL against all ones.
+ *
+ * create     sos_host [S][6].  RCFM_ERR_ARG before any device call: a NULL pointer, C < 1, ch outside {1, 2}, S outside
+ *            1 .. 8, a coefficient that is not finite, a0 != 1, an unstable section.  Everything a run needs is built here.
+ * run        filters rows [0, count) of `in` into `out` with the state slots of channels first .. first + count - 1,
+ *            asynchronously on `stream`, without a device allocation or a host synchronisation.  out == in is allowed; any
+ *            other overlap is the caller's error.  select: uint8 [count] on the device, or NULL for all; a row with
+ *            select[c] == 0 is copied unchanged (not touched at all in place) and its state does not advance.
+ *            RCFM_ERR_ARG before any device call: a NULL handle, in or out, count < 1, n < 1, a pointer not aligned for a
+ *            float.  RCFM_ERR_INDEX: first < 0 or first + count > C.
+ * reset      all states back to zero, on `stream`.
+ * get_state / set_state   the whole state, float64 [C][ch][S][2], to / from the host; both wait for `stream`.
+ * set_fence  as RCFM_OPT_STATE_FENCE: when on, a run waits for the event the previous run of this handle recorded and
+ *            records its own, so one handle may serve consecutive buffers on different streams.  Off by default, and then
+ *            no event is touched. */
+int rcfm_audio_filter_create(int C, int ch, int S, const double* sos_host, rcfm_audio_filter_t* out);
+int rcfm_audio_filter_run(rcfm_audio_filter_t f, int first, int count, int n, const void* in, void* out, const void* select,
+                          void* stream);
+int rcfm_audio_filter_reset(rcfm_audio_filter_t f, void* stream);
+int rcfm_audio_filter_get_state(rcfm_audio_filter_t f, double* state_host, void* stream);
+int rcfm_audio_filter_set_state(rcfm_audio_filter_t f, const double* state_host, void* stream);
+int rcfm_audio_filter_set_fence(rcfm_audio_filter_t f, int on);
+int rcfm_audio_filter_destroy(rcfm_audio_filter_t f);
 
 /* ---- host ingest (the step before Tuner.load) -------------------------------- */
 

@@ -33,7 +33,8 @@ RCFM_PACK_SEGMENT = 4096           # elements of a row one workgroup of the pack
 RCFM_IQ_BALANCE_OFF, RCFM_IQ_BALANCE_FIXED, RCFM_IQ_BALANCE_AUTO = 0, 1, 2   # rcfm_tuner_set_iq_balance
 RCFM_IQ_SEG_PAIRS, RCFM_IQ_MAX_SEGS = 16384, 1024   # mirror pairs per workgroup of an estimate, and the most workgroups (csrc/iq_balance.h)
 RCFM_TONE_MAX_K, RCFM_TONE_SEGMENT = 64, 8192    # tones of a bank; samples of a frame per workgroup (csrc/tones.h)
-RCFM_TUNER_OPT_NARROW_TILES, RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                              # rcfm_tuner_set_option
+RCFM_SOS_MAX_SECTIONS, RCFM_SOS_RUN, RCFM_SOS_SEGMENT = 8, 33, 8192    # sections of an audio filter; samples per thread; floats per sweep (csrc/audio_filter.h)
+RCFM_TUNER_OPT_NARROW_TILES,RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                              # rcfm_tuner_set_option
 
 _ERR_SIZE, _ERR_INDEX, _ERR_RUNTIME, _ERR_ARG, _ERR_STATE = -1, -2, -3, -4, -5
 
@@ -116,6 +117,13 @@ SIGNATURES = {
     "rcfm_tone_bank_run": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "rcfm_tone_bank_destroy": [_vp],
     "rcfm_tone_score": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "rcfm_audio_filter_create": [_i, _i, _i, ctypes.POINTER(_dbl), ctypes.POINTER(_vp)],
+    "rcfm_audio_filter_run": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "rcfm_audio_filter_reset": [_vp, _vp],
+    "rcfm_audio_filter_get_state": [_vp, ctypes.POINTER(_dbl), _vp],
+    "rcfm_audio_filter_set_state": [_vp, ctypes.POINTER(_dbl), _vp],
+    "rcfm_audio_filter_set_fence": [_vp, _i],
+    "rcfm_audio_filter_destroy": [_vp],
     "rcfm_drain_create": [_sz, _i, _i, ctypes.POINTER(_vp)],
     "rcfm_drain_begin": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)],
     "rcfm_drain_submit": [_vp, _vp],

@@ -15,4 +15,5 @@ from radiocore.tools.egress import *
 from radiocore.tools.lanes import *
 from radiocore.tools.arena import *
 from radiocore.tools.tonebank import *
-from radiocore.tools import iq, rds, tones
+from radiocore.tools.audiofilter import *
+from radiocore.tools import iq, rds, tones, audiofilter

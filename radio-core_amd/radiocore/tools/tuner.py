@@ -87,6 +87,10 @@ class Tuner(Injector):
         self._tones_dev = None     # (channel-list version, device int32 [C], device float32 [C]) of a tone squelch
         self._tone_out = None      # device (P, E) of the last run_all / run_each, one pair per launch group
         self._tones_ready = None   # (launch-plan key, the _tones it was checked for): the bank fits every group's audio length
+        self._afilt = None         # set_audio_filter: None (off) or (AudioFilter, uint8 [C] or None) (a new object per setting)
+        self._afilt_dev = None     # (channel-list version, device uint8 [C]) of the filter's channel selection
+        self._afilt_handles = {}   # (legs, A) -> (channels, AudioFilter, librcfm handle): the filter's states, by channel index
+        self._afilt_ready = None   # (launch-plan key, the _afilt it was checked for): the filter has a design for every group's audio rate
 
     @property
     def input_frequency(self) -> float:
@@ -126,6 +130,7 @@ class Tuner(Injector):
         """Forget all channels (raises ValueError like the reference: min() of nothing)."""
         self._bounds = []
         self._lo = self._hi = self._bw_sum = None
+        self._afilt_handles.clear()        # the audio filter's states belong to the channels
         self._recalculate()
 
     def _recalculate(self, added=None):
@@ -627,12 +632,93 @@ class Tuner(Injector):
                                          audio.numel() // count, hip.ptr(audio), hip.ptr(mask), s))
         return mask
 
+    # ---- audio filter (rcfm_audio_filter_run; no reference counterpart) ------------------------------------------------
+
+    def set_audio_filter(self, filt=None, channels=None):
+        """What a receiver applies to the audio before its speaker: with a ``radiocore.AudioFilter`` (for instance
+        ``radiocore.tools.audiofilter.VOICE_NFM``: the 300 Hz high-pass that strips the CTCSS tone, a 3 kHz low-pass and
+        narrow FM's de-emphasis), ``run_all`` / ``run_each`` / ``run_all_packed`` (and ``Lanes.submit``) filter every
+        group's audio in place behind its demodulators, on the caller's stream and without a host synchronisation.  The
+        filter runs behind the tone bank -- ``tone_power()`` sees the unfiltered audio -- and before the level squelch and
+        the tone squelch zero the closed rows; its state is one per channel (and leg), carried from buffer to buffer
+        whether the channel is open or not, kept when channels are added, zeroed by ``reset_states()`` and dropped by
+        ``reset()`` and by a new filter.  ``channels``: a bool per channel, or None for all.  ``None`` (the default) turns
+        it off: nothing more is launched than before.  ValueError, here or -- for channels added later -- in the next run
+        before anything of it is launched, for a filter without a design at a channel's audio rate (a corner at or above
+        half of it, ``sos`` sections of another rate) or a selection of another length; the setting in force stays."""
+        if filt is None:
+            if channels is not None:
+                raise ValueError("set_audio_filter: channels need a filter")
+            self._afilt = None
+            self._afilt_handles.clear()
+        else:
+            if not hasattr(filt, "sections") or not hasattr(filt, "_create"):
+                raise ValueError("set_audio_filter takes a radiocore.AudioFilter")
+            sel = None
+            if channels is not None:
+                sel = np.array(channels, dtype=bool).astype(np.uint8)
+                if sel.ndim != 1 or sel.shape[0] != len(self._bounds):
+                    raise ValueError("filtered channels: one bool per channel (%d)" % len(self._bounds))
+            setting = (filt, sel)
+            self._fit_afilt(setting)               # refused here, with the old setting still in force
+            if self._afilt is None or self._afilt[0] is not filt:
+                self._afilt_handles.clear()        # another filter: its states start at rest
+            self._afilt = setting
+        self._afilt_dev = None
+
+    def _fit_afilt(self, setting):
+        """The filter's design for the audio rate of every group of the launch plan, and the selection's length: whatever
+        is wrong raises here, before a run has advanced any state.  Once per (channel list, shard, setting)."""
+        if not self._bounds:
+            return
+        groups, first, count = self._launch_plan()
+        if self._afilt_ready is not None and self._afilt_ready[0] == self._plan[0] and self._afilt_ready[1] is setting:
+            return
+        if setting[1] is not None and setting[1].shape[0] != len(self._bounds):
+            raise ValueError("filtered channels were set for %d channels, the tuner has %d" % (setting[1].shape[0], len(self._bounds)))
+        for A in sorted({g[4] for g in groups if g[2] is not None}):
+            setting[0].sections(A)
+        self._afilt_ready = (self._plan[0], setting)
+
+    def _afilt_handle(self, ch, A):
+        # one handle per (legs, audio rate), sized for all channels: its state slots are addressed by channel index, so
+        # shard and regrouping keep them; a longer channel list takes the states over
+        C, filt = len(self._bounds), self._afilt[0]
+        ent = self._afilt_handles.get((ch, A))
+        if ent is not None and ent[0] == C and ent[1] is filt:
+            return ent[2].value
+        h = filt._create(C, ch, A)
+        if ent is not None and ent[1] is filt:
+            dp = ctypes.POINTER(ctypes.c_double)
+            old = np.zeros((ent[0], ch, len(filt), 2))
+            hip.check(self._lib.rcfm_audio_filter_get_state(ent[2].value, old.ctypes.data_as(dp), hip.stream()))
+            new = np.zeros((C, ch, len(filt), 2))
+            new[:min(C, ent[0])] = old[:min(C, ent[0])]
+            hip.check(self._lib.rcfm_audio_filter_set_state(h.value, new.ctypes.data_as(dp), hip.stream()))
+        if self._state_fence:
+            hip.check(self._lib.rcfm_audio_filter_set_fence(h.value, 1))
+        self._afilt_handles[(ch, A)] = (C, filt, h)
+        return h.value
+
+    def _filter_group(self, first, count, audio):
+        # behind the group's tone bank on the same stream, in place
+        sel = None
+        if self._afilt[1] is not None:
+            if self._afilt_dev is None or self._afilt_dev[0] != self._version:
+                self._afilt_dev = (self._version, hip.to_device(self._afilt[1]))
+            sel = ctypes.c_void_p(self._afilt_dev[1].data_ptr() + first)
+        A, ch = int(audio.shape[1]), int(audio.shape[2])
+        hip.check(self._lib.rcfm_audio_filter_run(self._afilt_handle(ch, A), first, count, A, hip.ptr(audio), hip.ptr(audio),
+                                                  sel, hip.stream()))
+
     def _gates(self, handle, first, count, audio):
-        """What follows a group's rcfm_pipeline_run on the same stream: the tone bank, the level squelch, the tone squelch,
-        each only when set.  (tones (P, E) or None, open mask or None)."""
+        """What follows a group's rcfm_pipeline_run on the same stream: the tone bank, the audio filter, the level squelch,
+        the tone squelch, each only when set.  (tones (P, E) or None, open mask or None)."""
         tones = mask = None
         if self._tones is not None:
             tones = self._tones[0].run(audio, step=int(audio.shape[2]), offset=0)
+        if self._afilt is not None:
+            self._filter_group(first, count, audio)
         if self._squelch is not None:
             mask = self._squelch_group(handle, first, count, audio)
         if tones is not None and self._tones[1] is not None:
@@ -697,6 +783,8 @@ class Tuner(Injector):
         ch = 2 if kind == hip.RCFM_WBFM else 1
         if self._tones is not None:
             self._fit_tones(self._tones)
+        if self._afilt is not None:
+            self._fit_afilt(self._afilt)
         audio = hip.empty((count, A, ch), self._torch.float32)
         hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk, *geo[4:]), first, count,
                                               hip.ptr(audio), hip.stream()))
@@ -777,6 +865,8 @@ class Tuner(Injector):
         tone_out = [] if self._tones is not None else None
         if self._tones is not None:
             self._fit_tones(self._tones)
+        if self._afilt is not None:
+            self._fit_afilt(self._afilt)
         for i, n, kind, B, A, tau, *agc in groups:
             if kind is None:
                 raise ValueError("run_each needs an FM, MFM, WBFM, AM, USB or LSB demodulator on every channel")
@@ -813,9 +903,11 @@ class Tuner(Injector):
     def reset_states(self):
         """Every channel's de-emphasis state back to the reference's freshly constructed filters (deemphasis.py:48-49),
         and every AGC back to "no history": the batched handles of run_all / run_each, whose slots the channels'
-        demodulator objects share."""
+        demodulator objects share.  The audio filter's states (set_audio_filter) go back to rest as well."""
         for h in self._batched.values():
             hip.check(self._lib.rcfm_demod_reset_state(h.value, hip.stream()))
+        for _, _, h in self._afilt_handles.values():
+            hip.check(self._lib.rcfm_audio_filter_reset(h.value, hip.stream()))
 
     def set_kernel_options(self, lds_chain=True, fused_tiles=True, phase_link=True, narrow_tiles=1, ssb_direct=True):
         """Which forms of the kernel chain run_all / run_each may use (rcfm_demod_set_option; no reference
@@ -895,6 +987,8 @@ class Tuner(Injector):
         for key, h in self._batched.items():
             if key[0] not in _STATELESS or _key_agc(key) is not None:
                 hip.check(self._lib.rcfm_demod_set_option(h.value, hip.RCFM_OPT_STATE_FENCE, 1))
+        for _, _, h in self._afilt_handles.values():
+            hip.check(self._lib.rcfm_audio_filter_set_fence(h.value, 1))
 
     def _lane_clone(self):
         """A second Tuner over the SAME channel list, demodulator objects and de-emphasis state, with its own device
@@ -910,6 +1004,9 @@ class Tuner(Injector):
             self._squelch, self._squelch_dev, self._open = base._squelch, None, None
         if self._tones is not base._tones:                 # ... its tone bank and tone squelch (a new object per set_tones)
             self._tones, self._tones_dev, self._tone_out, self._open, self._tones_ready = base._tones, None, None, None, None
+        if self._afilt is not base._afilt:                 # ... its audio filter (a new object per set_audio_filter) and that filter's states
+            self._afilt, self._afilt_dev, self._afilt_ready = base._afilt, None, None
+        self._afilt_handles = base._afilt_handles
         self._iq_balance = base._iq_balance                # ... its IQ balance (the next load applies it; per buffer, nothing to fence)
         if self._fine is not base._fine:                   # ... and its fine-tune (a new object per retune): the next load applies it
             self._fine, self._abi_arrays = base._fine, None
