@@ -55,7 +55,8 @@ extern "C" {
                             only; a handle that never calls rcfm_tuner_set_iq_balance launches what it launched before);
                             rcfm_tone_bank_* and rcfm_tone_score added (new symbols only, nothing existing changed; a frame
                             length above 2^24 is refused: an implementation limit, the definition itself has none);
-                            rcfm_audio_filter_* added (new symbols only, nothing existing changed) */
+                            rcfm_audio_filter_* added (new symbols only, nothing existing changed);
+                            rcfm_subcarrier_describe added to rcfm_tools.h (a new host-only symbol, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,

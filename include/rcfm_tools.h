@@ -126,6 +126,20 @@ int rcfm_fft_c2c_plan(int64_t n, const int64_t* pass_lengths, int npass, int lay
  * tools/bench_fft.py and the fallback for lengths the engine refuses. */
 int rcfm_fft_c2c_rocfft(int64_t n, int batch, int inverse, const void* in, void* out, void* stream);
 
+/* ---- subcarrier tap: the tile ------------------------------------------------------------------------------------ */
+
+/* Which tile rcfm_subcarrier_run / rcfm_pipeline_subcarrier (rcfm.h) use for decimation D = B / R and T taps -- the rule is
+ * a function of (D, T) alone (csrc/subcarrier.h, tap_tile):
+ *   J          outputs per workgroup, one of 1024, 512, 256, 128, 64, 32, 16, 8, 4; 0: no tile fits the LDS and the
+ *              one-output-per-workgroup kernel runs (rpad is still filled, Q and lds_bytes are 0)
+ *   rpad       taps per polyphase row, zero-padded to whole steps of four
+ *   Q          floats per polyphase row in LDS (J + rpad + 4)
+ *   lds_bytes  4 D Q, the dynamic LDS of a workgroup
+ * RCFM_ERR_ARG for what rcfm_subcarrier_create refuses (D < 1, T even, T outside 1 .. 4095) and for a NULL pointer.  No
+ * device call; what a test needs to know which tile it ran (tests/test_subcarrier_model.py holds the case table to
+ * every J). */
+int rcfm_subcarrier_describe(int D, int T, int* J, int* rpad, int* Q, int64_t* lds_bytes);
+
 /* ---- measurement ------------------------------------------------------------ */
 
 /* Per-stage timing with HIP events recorded on the stage's own stream (the reference

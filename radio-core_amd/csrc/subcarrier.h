@@ -22,7 +22,7 @@ struct TapTile {
 
 inline TapTile tap_tile(int D, int T) {
     TapTile t;
-    t.rpad = ((T + D - 1) / D + kTapBlock - 1) / kTapBlock * kTapBlock;
+    t.rpad = ((int)(((int64_t)T + D - 1) / D) + kTapBlock - 1) / kTapBlock * kTapBlock;   // (T + D in 64 bits: D reaches 2^31 - 1)
     for (int J : {1024, 512, 256, 128, 64, 32, 16, 8, 4}) {
         t.J = J;
         t.Q = J + t.rpad + kTapBlock;

@@ -319,6 +319,19 @@ int rcfm_pipeline_subcarrier(rcfm_tuner_t t, rcfm_subcarrier_t h, int first, int
     });
 }
 
+int rcfm_subcarrier_describe(int D, int T, int* J, int* rpad, int* Q, int64_t* lds_bytes) {
+    return guarded([&] {
+        RC_REQUIRE(J && rpad && Q && lds_bytes, RCFM_ERR_ARG, "NULL argument");
+        RC_REQUIRE(D >= 1, RCFM_ERR_ARG, "bad subcarrier tap size");
+        RC_REQUIRE(T >= 1 && T <= 4095 && T % 2 == 1, RCFM_ERR_ARG, "the number of taps must be odd, 1 .. 4095");
+        const TapTile tile = tap_tile(D, T);
+        *J = tile.J;
+        *rpad = tile.rpad;
+        *Q = tile.Q;
+        *lds_bytes = (int64_t)tile.lds_bytes(D);
+    });
+}
+
 int rcfm_subcarrier_destroy(rcfm_subcarrier_t h) {
     return guarded([&] { delete h; });
 }

@@ -104,6 +104,7 @@ SIGNATURES = {
     "rcfm_subcarrier_run": [_vp, _i, _vp, _vp, _vp],
     "rcfm_pipeline_subcarrier": [_vp, _vp, _i, _i, _vp, _vp],
     "rcfm_subcarrier_destroy": [_vp],
+    "rcfm_subcarrier_describe": [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)],
     "rcfm_host_register": [_vp, _sz],
     "rcfm_host_unregister": [_vp],
     "rcfm_feeder_create": [_sz, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp)],

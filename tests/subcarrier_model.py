@@ -26,21 +26,43 @@ import signal_edges
 import tuner_model
 
 ROWS = 3
-# (B, R, f, T): float32 yardstick (the figure test_subcarrier_model.py prints, plus a quarter)
+# (B, R, f, T): float32 yardstick (the figure test_subcarrier_model.py prints, plus a quarter).  Every comment names the
+# tile the kernel takes for the case's D = B / R and T, "J = <outputs per workgroup>" (0: the single-output kernel), as
+# rcfm_subcarrier_describe reports it: test_subcarrier_model.py holds the comments to the library and the table to every J.
 CASES = {
-    (240000, 9600, 57000, 241): 1.09e-6,   # 64-bit phase index, D = 25 (RDS) [measured 8.72e-7]
-    (12500, 500, 100, 151): 4.0e-7,        # a CTCSS tone of a narrow channel [measured 3.22e-7]
-    (6000, 6000, 0, 1): 2.8e-7,            # D = 1, one tap: y = d + 0j [measured 2.26e-7]
-    (6000, 240, 2999, 257): 7.6e-7,        # f next to B / 2, T > D [measured 6.07e-7]
-    (1000, 200, -300, 31): 2.4e-7,         # negative f, D = 5 [measured 1.94e-7]
-    (1001, 91, 77, 15): 2.0e-7,            # odd B: rows only 8-byte aligned [measured 1.63e-7]
-    (6000, 1, 1234, 4095): 2.0e-6,         # one output, the longest filter, D > T [measured 1.6e-6]
+    (240000, 9600, 57000, 241): 1.09e-6,   # 64-bit phase index, D = 25 (RDS), J = 256 [measured 8.72e-7]
+    (12500, 500, 100, 151): 4.0e-7,        # a CTCSS tone of a narrow channel, D = 25, J = 256 [measured 3.22e-7]
+    (6000, 6000, 0, 1): 2.8e-7,            # D = 1, one tap: y = d + 0j, J = 1024 [measured 2.26e-7]
+    (6000, 240, 2999, 257): 7.6e-7,        # f next to B / 2, T > D, D = 25, J = 256 [measured 6.07e-7]
+    (1000, 200, -300, 31): 2.4e-7,         # negative f, D = 5, J = 1024 [measured 1.94e-7]
+    (1001, 91, 77, 15): 2.0e-7,            # odd B: rows only 8-byte aligned, D = 11, J = 512 [measured 1.63e-7]
+    (6000, 1, 1234, 4095): 2.0e-6,         # one output, the longest filter, D = 6000 > T, J = 0 [measured 1.6e-6]
+    # every other tile, the deepest rows, the ragged last tiles and the mixed store paths
+    (12000, 6000, 1500, 4095): 2.8e-6,     # D = 2, J = 1024: rpad = 2048, 512 steps per row, a third of the outputs over a row end [measured 2.23e-6; MI355X 1.85e-6]
+    (12000, 4000, -2000, 257): 1.03e-6,    # D = 3, J = 1024: D does not divide the staging group of four samples [measured 8.27e-7; MI355X 6.19e-7]
+    (12500, 125, 1000, 241): 6.0e-7,       # D = 100, J = 128: half a wave computes, 125 of 128 outputs, R % 4 = 1 [measured 4.79e-7; MI355X 4.79e-7]
+    (20000, 100, 3000, 241): 5.85e-7,      # D = 200, J = 64: 16 lanes compute, second tile 36 of 64 [measured 4.68e-7; MI355X 4.96e-7]
+    (20000, 80, 3000, 241): 6.05e-7,       # D = 250, J = 32: three tiles, the last one 16 of 32 [measured 4.85e-7; MI355X 5.50e-7]
+    (24000, 48, 5000, 241): 4.7e-7,        # D = 500 > T, J = 16: one step per row, rows from T on carry no tap [measured 3.76e-7; MI355X 3.15e-7]
+    (20000, 20, 7000, 241): 6.35e-7,       # D = 1000, J = 8: the last tile 4 of 8 [measured 5.07e-7; MI355X 5.79e-7]
+    (27300, 20, 9000, 241): 3.55e-7,       # D = 1365, J = 4: the last tile that fits (65 520 bytes), one computing thread [measured 2.84e-7; MI355X 2.81e-7]
+    (27320, 20, 9000, 241): 4.1e-7,        # D = 1366, J = 0: its neighbour, the single-output kernel with T < 256 [measured 3.30e-7; MI355X 1.32e-7]
+    (24000, 24, -7000, 4095): 1.47e-6,     # D = 1000 < T, J = 4: rpad = 8 at the smallest tile, negative f [measured 1.18e-6; MI355X 1.67e-6]
+    (8190, 6, 100, 31): 2.6e-7,            # D = 1365, J = 4: R % 4 = 2 under 16-byte stores, the last tile holds 2 outputs [measured 2.09e-7; MI355X 1.37e-7]
+    (12500, 250, 19, 151): 3.55e-7,        # D = 50, J = 256: R % 4 = 2, one tile, its last computing lane stores 2 outputs [measured 2.84e-7; MI355X 3.59e-7]
 }
+# the cases whose row ends test_hip_subcarrier.py reports apart from the interior (edge_outputs)
+EDGE_CASES = ((12000, 6000, 1500, 4095), (6000, 240, 2999, 257))
 # a Tuner whose channels have a prime bandwidth (no engine plan: rocFFT, samples instead of phases): (n, B, R, f, T)
-PRIME_BAND = (90000, 3001, 3001, 700, 31)
+PRIME_BAND = (90000, 3001, 3001, 700, 31)      # D = 1, J = 1024
 PRIME_BAND_YARDSTICK = 1.45e-6          # measured 8.9e-7, 1.16e-6, 9.5e-7 on the three channels
+# two bands whose channels the engine plans (the Tuner hands over phases, k_subcarrier_tap<true>), built like the prime band
+PHASE_BAND_ONE = (100000, 12500, 125, 1000, 241)   # D = 100, J = 128: phase rows 16-byte aligned
+PHASE_BAND_ONE_YARDSTICK = 5.4e-7       # measured 2.4e-7, 4.3e-7, 4.3e-7 on the three channels; MI355X 5.2e-7, 8.4e-7, 7.6e-7
+PHASE_BAND_TWO = (81000, 10125, 81, 700, 31)       # D = 125, J = 64: B odd, phase rows only 4-byte aligned (scalar loads)
+PHASE_BAND_TWO_YARDSTICK = 3.7e-7       # measured 1.5e-7, 3.0e-7, 1.4e-7 on the three channels; MI355X 2.2e-7, 2.3e-7, 1.7e-7
 # the three RDS stations of rds_model.band() through the Tuner: R, f, T, cutoff; one yardstick per channel
-RDS_TAP = (9600, 57000, 241, 3000.0)
+RDS_TAP = (9600, 57000, 241, 3000.0)           # B = 240 000, D = 25, J = 256
 RDS_YARDSTICK = (2.45e-6, 3.55e-6, 4.2e-6)     # measured 1.95e-6, 2.82e-6, 3.35e-6 (amplitudes 0.3, 0.1, 0.06)
 
 
@@ -156,17 +178,15 @@ def rds_truth():
     return y
 
 
-def prime_band_centres():
-    B = PRIME_BAND[1]
+def band_centres(B):
     return [1e6 - 3 * B, 1e6, 1e6 + 3 * B]
 
 
 @functools.lru_cache(maxsize=None)
-def prime_band():
-    """(x [n] complex64, f_in, centres): three channels of prime bandwidth, each a smooth FM station
-    (signal_edges.dc_station at level 0: tones of 0.12 at 300 .. 1100 Hz, one of them at or next to the tap's 700 Hz)."""
-    n, B = PRIME_BAND[:2]
-    centres = prime_band_centres()
+def small_band(n, B):
+    """(x [n] complex64, f_in, centres): three channels of bandwidth B, each a smooth FM station (signal_edges.dc_station
+    at level 0: tones of 0.12 at 300 .. 1102 Hz, one of them at or next to the tap frequency of every band here)."""
+    centres = band_centres(B)
     f_in = 0.5 * (min(centres) + max(centres))
     st = [signal_edges.dc_station(B, i, 0.0) for i in range(len(centres))]
     x = signal_edges.wideband_from(st, n, f_in, centres, B, gain=(0.3, 0.1, 0.2))
@@ -175,13 +195,40 @@ def prime_band():
 
 
 @functools.lru_cache(maxsize=None)
-def prime_band_channels():
+def small_band_channels(n, B):
+    """(float64 channels [3][B], float32-model channels [3][B] complex64) of small_band(n, B) through tuner_model."""
     import scipy.fft
-    n, B = PRIME_BAND[:2]
-    x, f_in, centres = prime_band()
+    x, f_in, centres = small_band(n, B)
     rolls = _rolls(f_in, centres)
     X64 = np.fft.fft(x.astype(np.complex128))
     X32 = scipy.fft.fft(x)
     ref = np.array([tuner_model.ref_channel(X64, n, r, B) for r in rolls])
     low = np.array([tuner_model.f32_channel(X32, n, r, B) for r in rolls])
     return ref, low
+
+
+@functools.lru_cache(maxsize=None)
+def small_band_truth(band):
+    """[3][R] complex128, read-only: the tap of band = (n, B, R, f, T), float64 from the wideband buffer on."""
+    n, B, R, f, T = band
+    y = truth(small_band_channels(n, B)[0], R, f, taps(T))
+    y.setflags(write=False)
+    return y
+
+
+def prime_band_centres():
+    return band_centres(PRIME_BAND[1])
+
+
+def prime_band():
+    return small_band(*PRIME_BAND[:2])
+
+
+def prime_band_channels():
+    return small_band_channels(*PRIME_BAND[:2])
+
+
+def edge_outputs(B, R, T):
+    """How many outputs at a row's head reach in front of sample 1 (j D - c < 1; at its tail one fewer reaches past the
+    end, j D - c + T > B): the `edge` of primitives_model.segment_errors, whose tail takes one interior output along."""
+    return ((T - 1) // 2) // (B // R) + 1

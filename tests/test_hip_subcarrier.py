@@ -44,21 +44,45 @@ def _truth(case):
 _truth.cache = {}
 
 
+def _tile(hip, D, T):
+    """J of rcfm_subcarrier_describe: the outputs per workgroup the kernel takes (0: the single-output kernel)."""
+    J, rpad, Q, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    hip.check(hip.lib().rcfm_subcarrier_describe(D, T, ctypes.byref(J), ctypes.byref(rpad), ctypes.byref(Q), ctypes.byref(lds)))
+    return J.value
+
+
+def _segments(y, want, edge):
+    """primitives_model.segment_errors (head, interior, tail) of complex rows in row_errors' metric, |delta| / max|truth|:
+    the function takes real arrays, so it is given |truth| and |truth| + |delta|."""
+    mag = np.abs(np.asarray(want, np.complex128))
+    return pm.segment_errors(mag + np.abs(np.asarray(y, np.complex128) - want), mag, edge)
+
+
 # ---- the standalone cases ------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("batch", (1, 3))
 @pytest.mark.parametrize("case", list(sm.CASES), ids=lambda c: "B%d-R%d-f%d-T%d" % c)
-def test_case_within_its_bound(rc, case, batch):
+def test_case_within_its_bound(rc, hip, case, batch):
     B, R, f, T = case
     x = sm.case_input(B)[:batch]
     tap = rc.Subcarrier(B, R, f, sm.taps(T), batch=batch)
     y = tap.run(x[0] if batch == 1 else x)
     assert y.dtype == np.complex64 and y.shape == ((R,) if batch == 1 else (batch, R))
-    err = pm.row_errors(y.reshape(batch, R), _truth(case)[:batch])
+    y, want = y.reshape(batch, R), _truth(case)[:batch]
+    err = pm.row_errors(y, want)
     bound = pm.gpu_bound(sm.CASES[case])
-    print("B = %d, R = %d, f = %d, T = %d, batch %d: worst row %d at %.3g, bound %.3g"
-          % (B, R, f, T, batch, int(np.argmax(err)), float(np.max(err)), bound))
+    print("B = %d, R = %d, f = %d, T = %d (J = %d), batch %d: worst row %d at %.3g, bound %.3g"
+          % (B, R, f, T, _tile(hip, B // R, T), batch, int(np.argmax(err)), float(np.max(err)), bound))
     assert np.max(err) <= bound
+    if case in sm.EDGE_CASES:
+        # the outputs whose taps reach beyond the row (zero extension, d[0] = 0) apart from the interior, each against the
+        # whole row's peak: what the staging does at a row's ends is not read off a figure the interior dominates
+        edge = sm.edge_outputs(B, R, T)
+        assert 0 < edge and 2 * edge < R
+        head, interior, tail = _segments(y, want, edge)
+        print("    %d outputs at either row end: head %.3g, tail %.3g; interior %.3g" % (edge, head, tail, interior))
+        assert head <= bound and tail <= bound
+        assert interior <= bound
 
 
 def _raw_run(hip, handle, x_dev, count, R, stream=None):
@@ -70,7 +94,8 @@ def _raw_run(hip, handle, x_dev, count, R, stream=None):
     return y.cpu().numpy()
 
 
-@pytest.mark.parametrize("case", [(240000, 9600, 57000, 241), (1001, 91, 77, 15), (6000, 240, 2999, 257), (6000, 1, 1234, 4095)],
+@pytest.mark.parametrize("case", [(240000, 9600, 57000, 241), (1001, 91, 77, 15), (6000, 240, 2999, 257), (6000, 1, 1234, 4095),
+                                  (12500, 125, 1000, 241), (27300, 20, 9000, 241), (12000, 6000, 1500, 4095)],   # J = 128, J = 4, deep rows
                          ids=lambda c: "B%d-R%d-f%d-T%d" % c)
 def test_sub_range_stream_and_chunk_are_bit_identical(rc, hip, case):
     import torch
@@ -204,6 +229,125 @@ def test_band_without_phase_output(rc, hip):
     iq = tuner.run_channels(0, 3)
     direct = rc.Subcarrier(B, R, f, sm.taps(T), batch=3).run(iq)
     assert np.array_equal(direct.view(np.uint32), y.view(np.uint32))
+
+
+# ---- the from-phase form beyond RDS, the pipeline's chunk loop, shard ---------------------------------------------------------------
+
+PHASE_BANDS = {"one": (sm.PHASE_BAND_ONE, sm.PHASE_BAND_ONE_YARDSTICK), "two": (sm.PHASE_BAND_TWO, sm.PHASE_BAND_TWO_YARDSTICK)}
+
+
+def _phase_band_tuner(rc, hip, band):
+    """A Tuner over sm.small_band of `band`, not loaded; the engine plans B, so its channels are handed over as phases."""
+    n, B, R, f, T = band
+    plan = hip.FftPlan()
+    assert hip.lib().rcfm_fft_describe(B, 0, ctypes.byref(plan)) == 0, "the engine lost its plan for this length: pick another"
+    x, f_in, centres = sm.small_band(n, B)
+    tuner = rc.Tuner()
+    for fc in centres:
+        tuner.add_channel(fc, B, rc.FM(B, B // 5))
+    tuner.request_bandwidth(float(n))
+    assert tuner.input_frequency == f_in
+    return tuner
+
+
+@pytest.mark.parametrize("name", list(PHASE_BANDS))
+def test_band_with_phase_output(rc, hip, name):
+    """k_subcarrier_tap<true> at tiles other than RDS's: band one with 16-byte phase rows (J = 128), band two with an odd
+    B, whose phase rows are only 4-byte aligned (J = 64, scalar loads)."""
+    band, yardstick = PHASE_BANDS[name]
+    n, B, R, f, T = band
+    tuner = _phase_band_tuner(rc, hip, band)
+    tuner.load(sm.small_band(n, B)[0].copy())
+    tap = rc.Subcarrier(B, R, f, sm.taps(T))
+    y = tuner.subcarrier(tap)
+    assert y.dtype == np.complex64 and y.shape == (3, R)
+    want = sm.small_band_truth(band)
+    bound = pm.gpu_bound(yardstick)
+    err = pm.row_errors(y, want)
+    # the from-samples form on the Tuner's own channel samples: another kernel instance on another input (the samples
+    # instead of their phases), so within the bound of the truth, not bit for bit
+    direct = rc.Subcarrier(B, R, f, sm.taps(T), batch=3).run(tuner.run_channels(0, 3))
+    err_direct = pm.row_errors(direct, want)
+    for k in range(3):
+        print("phase band %s (B = %d, R = %d, f = %d, T = %d, J = %d), channel %d: from phases %.3g, from samples %.3g, bound %.3g"
+              % (name, B, R, f, T, _tile(hip, B // R, T), k, err[k], err_direct[k], bound))
+    assert np.all(err <= bound)
+    assert np.all(err_direct <= bound)
+
+
+def _rds_setup(rc, hip):
+    from radiocore.tools import rds
+    R, f, T, cutoff = sm.RDS_TAP
+
+    def make():
+        tuner = rc.Tuner()
+        for fc in rds_model.CENTRES:
+            tuner.add_channel(fc, rds_model.B, rc.WBFM(rds_model.B, 48000))
+        tuner.request_bandwidth(float(rds_model.N))
+        return tuner
+
+    return make, rc.Subcarrier(rds_model.B, R, f, rds.taps(rds_model.B, R, T, cutoff)), rds_model.band(), R
+
+
+def _band_one_setup(rc, hip):
+    n, B, R, f, T = sm.PHASE_BAND_ONE
+    return (lambda: _phase_band_tuner(rc, hip, sm.PHASE_BAND_ONE)), rc.Subcarrier(B, R, f, sm.taps(T)), sm.small_band(n, B)[0], R
+
+
+TAPPED_BANDS = {"rds": _rds_setup, "one": _band_one_setup}
+
+
+@pytest.mark.parametrize("name", list(TAPPED_BANDS))
+def test_pipeline_chunks_are_bit_identical(rc, hip, name):
+    """rcfm_pipeline_subcarrier with a handle whose chunk is below the count: several rounds of the Tuner's inverse FFT and
+    the tap kernel through ONE workspace, one channel (chunk 1) and two plus one (chunk 2) at a time."""
+    import torch
+    make, tap, x, R = TAPPED_BANDS[name](rc, hip)
+    tuner = make()
+    tuner.load(x.copy())
+    y = tuner.subcarrier(tap)                        # the Tuner's own handle: chunk 0, all three channels in one round
+    assert y.shape == (3, R) and np.all(np.isfinite(y.view(np.float32)))
+    handle = tuner._ready()
+    for chunk in (1, 2):
+        batched = tap._create(3, chunk)
+        out = torch.full((3, R), float("nan"), dtype=torch.complex64, device="cuda")
+        hip.check(hip.lib().rcfm_pipeline_subcarrier(handle, batched.value, 0, 3, hip.ptr(out), hip.stream()))
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        assert not np.any(np.isnan(got.view(np.float32))), chunk
+        assert np.array_equal(got.view(np.uint32), y.view(np.uint32)), chunk
+        # a sub-range that starts inside the handle's second round
+        out.fill_(float("nan"))
+        hip.check(hip.lib().rcfm_pipeline_subcarrier(handle, batched.value, 1, 2, hip.ptr(out), hip.stream()))
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        assert np.array_equal(got[:2].view(np.uint32), y[1:].view(np.uint32)), chunk
+        assert np.all(np.isnan(got[2].real)), chunk                    # nothing is written beyond `count` rows (NaN + 0j)
+
+
+@pytest.mark.parametrize("name", list(TAPPED_BANDS))
+def test_tap_after_shard(rc, hip, name):
+    """After shard(1, 2) and a fresh load the spectrum holds the bins of channels 1 - 2 only: the tap of those two is that
+    of the whole load bit for bit, channel 0 is refused by the library, and the audio is that of a tuner never tapped."""
+    make, tap, x, R = TAPPED_BANDS[name](rc, hip)
+    tuner = make()
+    tuner.load(x.copy())
+    y = tuner.subcarrier(tap)
+    tuner.shard(1, 2)
+    tuner.load(x.copy())
+    part = tuner.subcarrier(tap)
+    assert part.dtype == np.complex64 and part.shape == (2, R)
+    assert np.array_equal(part.view(np.uint32), y[1:3].view(np.uint32))
+    with pytest.raises(RuntimeError, match="shard"):
+        tuner.subcarrier(tap, first=0, count=1)
+    assert np.array_equal(tuner.subcarrier(tap, first=2, count=1).view(np.uint32), y[2:3].view(np.uint32))
+    audio = tuner.run_all()
+    twin = make()
+    twin.shard(1, 2)
+    twin.load(x.copy())
+    want = twin.run_all()
+    assert audio.shape == want.shape and audio.shape[0] == 2
+    assert np.array_equal(audio, want)
 
 
 def test_tap_follows_a_growing_channel_list(rc):

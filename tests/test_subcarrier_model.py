@@ -1,9 +1,12 @@
 """CPU: the subcarrier tap's model (tests/subcarrier_model.py) -- every float32 yardstick the GPU test derives its bounds
 from is evaluated here and lies below its pinned constant, the inputs keep the discriminator well conditioned, the
-vectorised truth is the literal definition -- and rcfm_subcarrier_create's argument errors, which need no device.
+vectorised truth is the literal definition -- and what needs no device of the library: rcfm_subcarrier_create's argument
+errors, and rcfm_subcarrier_describe, by which the case table is held to every tile the kernel can take.
 """
 
 import ctypes
+import inspect
+import re
 
 import numpy as np
 import pytest
@@ -34,6 +37,64 @@ def test_inputs_keep_the_discriminator_conditioned(B):
     assert np.max(np.abs(sm.discriminator(sm.case_input(B)))) <= signal_edges.STEP_BOUND
 
 
+LDS_WIDE, LDS_MAX = 32 * 1024, 64 * 1024        # csrc/subcarrier.h: kTapWideLds (tiles of J > 256), kTapMaxLds
+TILES = {0, 4, 8, 16, 32, 64, 128, 256, 512, 1024}
+
+
+def describe(D, T):
+    """(J, rpad, Q, lds_bytes) of rcfm_subcarrier_describe."""
+    from radiocore._internal import hip
+    J, rpad, Q, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    assert hip.lib().rcfm_subcarrier_describe(D, T, ctypes.byref(J), ctypes.byref(rpad), ctypes.byref(Q), ctypes.byref(lds)) == 0
+    return J.value, rpad.value, Q.value, lds.value
+
+
+def test_the_cases_reach_every_tile():
+    """Every outcome of tap_tile (csrc/subcarrier.h) is run by a case, both neighbours of the last tile that fits are, and
+    each case's comment names the J the library reports: a table that changes there shows here which case to add."""
+    source = inspect.getsource(sm).splitlines()
+    named = [(repr(case), case[0] // case[1], case[3]) for case in sm.CASES]
+    named.append((repr(sm.RDS_TAP), rds_model.B // sm.RDS_TAP[0], sm.RDS_TAP[2]))
+    named += [(repr(band), band[1] // band[2], band[4]) for band in (sm.PRIME_BAND, sm.PHASE_BAND_ONE, sm.PHASE_BAND_TWO)]
+    seen = {}
+    for text, D, T in named:
+        J, rpad, Q, lds = describe(D, T)
+        print("%s: D = %d, T = %d -> J = %d, rpad = %d, Q = %d, %d bytes of LDS" % (text, D, T, J, rpad, Q, lds))
+        lines = [ln for ln in source if text in ln and "#" in ln]
+        assert len(lines) == 1, text
+        comment = lines[0].split("#", 1)[1]
+        assert re.findall(r"\bJ = (\d+)\b", comment) == [str(J)], (text, J, comment)
+        assert rpad == ((T + D - 1) // D + 3) // 4 * 4
+        if J:
+            assert Q == J + rpad + 4 and lds == 4 * D * Q
+            assert lds <= (LDS_WIDE if J > 256 else LDS_MAX), (text, J, lds)
+        else:
+            assert Q == 0 and lds == 0
+        seen.setdefault(J, []).append((D, T))
+    assert set(seen) == TILES, sorted(TILES - set(seen))
+    # the last D with a tile and the first without one, both at a T no longer than a row
+    assert any(D == 1365 and T <= 1365 for D, T in seen[4]) and any(D == 1366 and T <= 1365 for D, T in seen[0])
+    # with T <= D every polyphase row holds one tap: 1365 rows of 12 floats are the last that fit 64 KiB
+    assert describe(1365, 1365)[0] == 4 and describe(1366, 1365)[0] == 0
+
+
+def test_describe_refuses_what_create_refuses():
+    from radiocore._internal import hip
+    lib = hip.lib()
+    J, rpad, Q, lds = ctypes.c_int(7), ctypes.c_int(7), ctypes.c_int(7), ctypes.c_int64(7)
+    out = (ctypes.byref(J), ctypes.byref(rpad), ctypes.byref(Q), ctypes.byref(lds))
+    for what, D, T in (("D < 1", 0, 3), ("negative D", -5, 3), ("even T", 25, 240), ("no taps", 25, 0), ("too many taps", 25, 4097),
+                       ("negative T", 25, -1)):
+        assert lib.rcfm_subcarrier_describe(D, T, *out) == -4, what
+        assert lib.rcfm_last_error(), what
+    assert (J.value, rpad.value, Q.value, lds.value) == (7, 7, 7, 7)
+    assert lib.rcfm_subcarrier_describe(25, 241, None, out[1], out[2], out[3]) == -4
+    assert lib.rcfm_subcarrier_describe(25, 241, out[0], out[1], out[2], None) == -4
+    assert describe(25, 241) == (256, 12, 272, 27200)          # RDS (DESIGN.md: 27.2 KB)
+    assert describe(1, 4095) == (1024, 4096, 5124, 20496)      # the deepest row
+    assert describe(2 ** 31 - 1, 1) == (0, 4, 0, 0) and describe(2 ** 31 - 1, 4095) == (0, 4, 0, 0)    # T + D - 1 beyond 32 bits
+
+
 def test_tuner_cases_yardsticks_and_conditioning():
     R, f, T, cutoff = sm.RDS_TAP
     ref, low = sm.rds_channels()
@@ -48,6 +109,15 @@ def test_tuner_cases_yardsticks_and_conditioning():
     err = pm.worst_row(sm.f32(low, R, f, sm.taps(T)), sm.truth(ref, R, f, sm.taps(T)))
     print("prime band: float32 %.3g, pinned %.3g" % (err, sm.PRIME_BAND_YARDSTICK))
     assert sm.PRIME_BAND_YARDSTICK / 2.5 <= err <= sm.PRIME_BAND_YARDSTICK
+    for name, band, pinned in (("phase band one", sm.PHASE_BAND_ONE, sm.PHASE_BAND_ONE_YARDSTICK),
+                               ("phase band two", sm.PHASE_BAND_TWO, sm.PHASE_BAND_TWO_YARDSTICK)):
+        n, B, R, f, T = band
+        ref, low = sm.small_band_channels(n, B)
+        assert np.max(np.abs(sm.discriminator(ref))) <= signal_edges.STEP_BOUND
+        err = pm.row_errors(sm.f32(low, R, f, sm.taps(T)), sm.small_band_truth(band))
+        print("%s: float32 per channel %s, pinned %.3g, device bound %.3g" % (name, err, pinned, pm.gpu_bound(pinned)))
+        assert pinned / 2.5 <= np.max(err) <= pinned
+        assert np.all(np.max(np.abs(sm.small_band_truth(band)), axis=1) > 0)
 
 
 def test_truth_is_the_literal_double_loop():
