@@ -7,6 +7,14 @@
  * oracle; then the same buffers through the rotating FFT owner's protocol and through two lanes (two streams), both
  * required to reproduce that audio bit for bit.
  *
+ * A host on a band with impulse noise (ignition, switching supplies) adds one call per buffer, between the feeder's acquire
+ * and the load, on the same stream -- no tuner entry point changes:
+ *     rcfm_blanker_create(N, 4096, 4, RCFM_BLANK_MEDIAN, 15.85, hold, ramp, R, &nb);     once: 12 dB over the median level
+ *     rcfm_blanker_run(nb, RCFM_IQ_CF32, N, x, x, NULL, stream);                         per buffer, in place
+ *     rcfm_tuner_load(t, x, stream);
+ * with ramp [R] the host's own float table in [0, 1] (include/rcfm.h, "noise blanker"); a host with two lanes keeps one
+ * blanker handle per lane.  This example's stations carry no pulses and it does not call it.
+ *
  *   gcc -O2 -Iinclude examples/c_host.c -Lradio-core_amd/radiocore/_lib -lrcfm -lm \
  *       -Wl,-rpath,$PWD/radio-core_amd/radiocore/_lib -o examples/c_host
  *   examples/c_host out_dir          (needs an MI355X)

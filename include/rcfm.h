@@ -56,7 +56,9 @@ extern "C" {
                             rcfm_tone_bank_* and rcfm_tone_score added (new symbols only, nothing existing changed; a frame
                             length above 2^24 is refused: an implementation limit, the definition itself has none);
                             rcfm_audio_filter_* added (new symbols only, nothing existing changed);
-                            rcfm_subcarrier_describe added to rcfm_tools.h (a new host-only symbol, nothing existing changed) */
+                            rcfm_subcarrier_describe added to rcfm_tools.h (a new host-only symbol, nothing existing changed);
+                            rcfm_blanker_* added, rcfm_blanker_last in rcfm_tools.h, RCFM_IQ_CF32 = 0 named (new symbols only,
+                            nothing existing changed: the load entry points refuse format 0 as before) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -134,6 +136,9 @@ int rcfm_tuner_load(rcfm_tuner_t t, const void* x, void* stream);
  *   RCFM_IQ_CS8   int8   (HackRF)                                     (float)i * 2^-7
  *   RCFM_IQ_CU8   uint8  (RTL-SDR; the centre is 127.5)               ((float)u - 127.5f) * 2^-7   (255 -> 0.99609375) */
 enum { RCFM_IQ_CS16 = 1, RCFM_IQ_CS8 = 2, RCFM_IQ_CU8 = 3 };
+/* The fourth value of the same enumeration, complex64 itself: a format of rcfm_blanker_run only -- rcfm_tuner_load_raw and
+ * rcfm_iq_convert refuse it like any other value they do not convert. */
+enum { RCFM_IQ_CF32 = 0 };
 /* rcfm_tuner_load of a raw buffer, x: [n][2] of the format's integer type on the device: the spectrum (halos, shard window,
  * held bins) is bit for bit that of rcfm_tuner_load of the converted samples, and the same refusals apply.  Where the
  * handle's wideband FFT runs on the engine, the conversion rides on the first pass's load (the buffer is read once, at 4
@@ -592,6 +597,63 @@ int rcfm_audio_filter_get_state(rcfm_audio_filter_t f, double* state_host, void*
 int rcfm_audio_filter_set_state(rcfm_audio_filter_t f, const double* state_host, void* stream);
 int rcfm_audio_filter_set_fence(rcfm_audio_filter_t f, int on);
 int rcfm_audio_filter_destroy(rcfm_audio_filter_t f);
+
+/* ---- noise blanker: impulse noise removed from the wideband buffer, ahead of the FFT (no reference counterpart) -----------
+ * A pulse of a few samples (ignition, switching supplies, electric fences) is white across the band: after rcfm_tuner_load it
+ * sits in every channel at once and nothing can remove it.  It can be removed where it is still a few samples long, in the
+ * time-domain buffer.  A C host calls rcfm_blanker_run before rcfm_tuner_load / rcfm_tuner_load_raw on the same stream; no
+ * rcfm_tuner_* entry point knows of it.
+ *
+ * Input.  n samples of one of four formats: RCFM_IQ_CF32 (complex64) or the three integer formats of rcfm_tuner_load_raw,
+ * converted to float32 by the rules given there, which are exact.
+ * A handle has
+ *   L       the block length, a power of two, 64 <= L <= 2^20;
+ *   W       the half-span in blocks, 0 <= W <= 8;
+ *   mode    RCFM_BLANK_MEDIAN or RCFM_BLANK_ABSOLUTE, and a double `value`: the threshold ratio (linear, in power) or the
+ *           absolute threshold (the power of a sample, full scale 1.0);
+ *   H       hold, H >= 0 samples;
+ *   ramp[R] float32, supplied by the host, every value in [0, 1], R >= 0;  G = H + R <= 1024.
+ * Sample power.  p[i] = fl32(fl32(re re) + fl32(im im)): two products and a sum, each rounded on its own, never an FMA.
+ * Block level.  Block b = i >> log2 L, nb = ceil(n / L); the last block may be short.  m[b] is the mean over the block's own
+ *   samples of (double)re^2 + (double)im^2, summed in float64 as the pairwise tree over the block's L slots (node j of a
+ *   level = node 2 j + node 2 j + 1 of the level below, slots at and beyond n being zero) and divided by the number of
+ *   samples: the order is a function of (n, L) alone and there are no floating-point atomics.  A non-finite m[b] counts as +inf.
+ * Threshold.  RCFM_BLANK_MEDIAN: r[b] is the lower median of m over blocks max(0, b - W) .. min(nb - 1, b + W), the element
+ *   (cnt - 1) / 2 of the ascending sort; t[b] = (float)(value r[b]), one rounding of the float64 product.  A pulse inflates the
+ *   mean of its own block many times over, but not the median of nine blocks.  RCFM_BLANK_ABSOLUTE: t[b] = (float)value for
+ *   every block; neither the level pass nor the median pass is launched.
+ * Hit.  hit[i] = p[i] > t[b(i)]; a NaN on either side gives no hit.
+ * Distance.  d[i] = min |i - j| over the hit samples j, infinite where the buffer has none.  Distances do not wrap at the
+ *   buffer's ends and nothing is carried from buffer to buffer: the stage has no state, and lanes need no fence.
+ * Gain.  g[i] = 0 for d <= H, ramp[d - H - 1] for H < d <= G, 1 beyond G.
+ * Output.  g = 1: the sample is copied bit for bit (NaN payloads and -0 survive); with out == in it is not written at all.
+ *   g = 0: complex64 stores (+0.0, +0.0), CS16 / CS8 store 0, CU8 stores I = Q = 127 + (i & 1) -- the centre 127.5 is not a
+ *   code, and alternating around it leaves no DC step.
+ *   otherwise: complex64 stores (fl32(g re), fl32(g im)); CS16 / CS8 store (int)rintf(fl32(g (float)v)) of each integer v;
+ *   CU8 stores (int)rintf(fl32(127.5f + fl32(g fl32((float)u - 127.5f)))).
+ * Stats.  Optionally a device int64 [2]: the number of hits and the number of samples with g < 1 (integer atomics: counts do
+ *   not depend on order).
+ * Determinism.  Output and stats are bit-identical from run to run, from stream to stream, in place and out of place, and
+ *   wherever the buffers lie within their alignment.
+ *
+ * create   ramp_host [ramp] (may be NULL when ramp == 0).  The handle owns its scratch -- block sums, thresholds, and the hit
+ *          mask of ceil(n_max / 4096) x 128 words -- allocated here, never in run.  RCFM_ERR_ARG before any device call: a NULL
+ *          out, n_max outside 1 .. 2^40, a block that is not a power of two or outside 64 .. 2^20, span outside 0 .. 8, an
+ *          unknown mode, a value that is not finite or is <= 0, hold < 0, ramp < 0, hold + ramp > 1024, a NULL ramp table
+ *          with ramp > 0, a ramp value outside [0, 1] or not finite.
+ * run      in -> out, n samples of `format`, asynchronously on `stream`, without a device allocation or a host
+ *          synchronisation.  out == in is allowed and is the cheap form (a tile without a hit nearby is not touched); any
+ *          other overlap of the two byte ranges is refused.  in and out are aligned for one sample: 8, 4 or 2 bytes; stats
+ *          for an int64.  n = 0 is a no-op that zeroes stats.  Runs of ONE handle share its scratch: order them on one
+ *          stream at a time (a host with several lanes keeps a handle per lane).
+ *          RCFM_ERR_ARG before any device call: a NULL handle or buffer, n < 0 or n > n_max, an unknown format,
+ *          misalignment, partial overlap. */
+typedef struct rcfm_blanker* rcfm_blanker_t;
+enum { RCFM_BLANK_MEDIAN = 0, RCFM_BLANK_ABSOLUTE = 1 };
+int rcfm_blanker_create(int64_t n_max, int block, int span, int mode, double value, int hold, const float* ramp_host, int ramp,
+                        rcfm_blanker_t* out);
+int rcfm_blanker_run(rcfm_blanker_t b, int format, int64_t n, const void* in, void* out, void* stats, void* stream);
+int rcfm_blanker_destroy(rcfm_blanker_t b);
 
 /* ---- host ingest (the step before Tuner.load) -------------------------------- */
 

@@ -140,6 +140,14 @@ int rcfm_fft_c2c_rocfft(int64_t n, int batch, int inverse, const void* in, void*
  * every J). */
 int rcfm_subcarrier_describe(int D, int T, int* J, int* rpad, int* Q, int64_t* lds_bytes);
 
+/* ---- noise blanker: what the last run decided --------------------------------------------------------------------- */
+
+/* The thresholds t [nb] float32 and the hit bitmask that the handle's last rcfm_blanker_run (rcfm.h) left, both on the device
+ * and valid once that run's stream has finished; any of the three pointers may be NULL.  Bit i & 31 of word i >> 5 is hit[i];
+ * bits at and beyond n are zero, up to the end of the last tile of 4096 samples.  nb = ceil(n / L), 0 before the first run
+ * and after a run of n = 0.  What the tests compare with the model (tests/blanker_model.py). */
+int rcfm_blanker_last(rcfm_blanker_t b, void** t_dev, void** hit_words_dev, int64_t* nb);
+
 /* ---- measurement ------------------------------------------------------------ */
 
 /* Per-stage timing with HIP events recorded on the stage's own stream (the reference

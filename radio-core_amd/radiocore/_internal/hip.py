@@ -28,6 +28,9 @@ RCFM_OPT_LDS_CHAIN, RCFM_OPT_FUSED_TILES, RCFM_OPT_PHASE_LINK, RCFM_OPT_NARROW_T
 RCFM_OPT_PILOT_CHAIN, RCFM_OPT_DECIM_TILE, RCFM_OPT_LDS_DEEMPH, RCFM_OPT_PILOT_BLOCKED, RCFM_OPT_GRAPH = 6, 7, 8, 9, 10
 RCFM_OPT_SSB_DIRECT = 11
 RCFM_IQ_CS16, RCFM_IQ_CS8, RCFM_IQ_CU8 = 1, 2, 3                  # rcfm_tuner_load_raw, rcfm_iq_convert
+RCFM_IQ_CF32 = 0                                                  # rcfm_blanker_run only: complex64 itself
+RCFM_BLANK_MEDIAN, RCFM_BLANK_ABSOLUTE = 0, 1                     # rcfm_blanker_create
+RCFM_BLANK_MIN_BLOCK, RCFM_BLANK_MAX_BLOCK, RCFM_BLANK_MAX_SPAN, RCFM_BLANK_MAX_GUARD = 64, 1 << 20, 8, 1024   # csrc/blanker.h
 RCFM_PCM_F32, RCFM_PCM_S16 = 0, 1                                 # rcfm_audio_pack
 RCFM_PACK_SEGMENT = 4096           # elements of a row one workgroup of the pack kernel takes per sweep (csrc/egress_kernel.h, kPackSegment)
 RCFM_IQ_BALANCE_OFF, RCFM_IQ_BALANCE_FIXED, RCFM_IQ_BALANCE_AUTO = 0, 1, 2   # rcfm_tuner_set_iq_balance
@@ -125,6 +128,10 @@ SIGNATURES = {
     "rcfm_audio_filter_set_state": [_vp, ctypes.POINTER(_dbl), _vp],
     "rcfm_audio_filter_set_fence": [_vp, _i],
     "rcfm_audio_filter_destroy": [_vp],
+    "rcfm_blanker_create": [_i64, _i, _i, _i, _dbl, _i, _fp, _i, ctypes.POINTER(_vp)],
+    "rcfm_blanker_run": [_vp, _i, _i64, _vp, _vp, _vp, _vp],
+    "rcfm_blanker_destroy": [_vp],
+    "rcfm_blanker_last": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64)],
     "rcfm_drain_create": [_sz, _i, _i, ctypes.POINTER(_vp)],
     "rcfm_drain_begin": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)],
     "rcfm_drain_submit": [_vp, _vp],

@@ -16,4 +16,5 @@ from radiocore.tools.lanes import *
 from radiocore.tools.arena import *
 from radiocore.tools.tonebank import *
 from radiocore.tools.audiofilter import *
+from radiocore.tools.blanker import *
 from radiocore.tools import iq, rds, tones, audiofilter

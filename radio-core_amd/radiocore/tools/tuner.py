@@ -91,6 +91,10 @@ class Tuner(Injector):
         self._afilt_dev = None     # (channel-list version, device uint8 [C]) of the filter's channel selection
         self._afilt_handles = {}   # (legs, A) -> (channels, AudioFilter, librcfm handle): the filter's states, by channel index
         self._afilt_ready = None   # (launch-plan key, the _afilt it was checked for): the filter has a design for every group's audio rate
+        self._blanker = None       # set_blanker: None (off) or (NoiseBlanker, in_place) (a new object per setting)
+        self._blank_handles = {}   # buffer length n -> (the NoiseBlanker it was made by, librcfm handle): this device tuner's own scratch
+        self._blank_scratch = None # the blanked copy of a caller's device tensor (buffer's dtype and size; allocated by the first such load)
+        self._blank_counts = None  # device int64 [2] of the last load with a blanker: hits, samples with gain below 1
 
     @property
     def input_frequency(self) -> float:
@@ -210,7 +214,8 @@ class Tuner(Injector):
         whole=True (multi-GPU, rotating FFT owner): keep every row any channel reads although this process is
         sharded -- the spectrum is about to be handed to the other ranks (sharding.SpectrumRing)."""
         x = hip.to_device(input_signal, self._torch.complex64)
-        self._load(x, int(x.shape[0]), whole, lambda h: self._lib.rcfm_tuner_load(h, hip.ptr(x), hip.stream()))
+        self._load(x, int(x.shape[0]), whole, lambda h, src: self._lib.rcfm_tuner_load(h, hip.ptr(src), hip.stream()),
+                   hip.RCFM_IQ_CF32, input_signal)
 
     def load_raw(self, samples, whole=False):
         """``load`` of a buffer as the receiver delivers it (rcfm_tuner_load_raw; no reference counterpart): a numpy array
@@ -222,11 +227,20 @@ class Tuner(Injector):
         x, fmt, n = iq.device_pairs(samples)
         if n != int(self._input_bandwidth):
             raise ValueError("input_sig size and input_size mismatch")
-        self._load(x, n, whole, lambda h: self._lib.rcfm_tuner_load_raw(h, fmt, hip.ptr(x), hip.stream()))
+        self._load(x, n, whole, lambda h, src: self._lib.rcfm_tuner_load_raw(h, fmt, hip.ptr(src), hip.stream()),
+                   fmt, samples)
 
-    def _load(self, x, n, whole, call):
-        # what load and load_raw share: `call(handle)` is the library's load of the device buffer x (n samples)
+    def _is_upload(self, given, x):
+        # True when the device buffer x is a tensor made for this load (a host array's upload, a converted copy), not the
+        # caller's own device tensor
+        return not (isinstance(given, self._torch.Tensor) and given.is_cuda and given.data_ptr() == x.data_ptr())
+
+    def _load(self, x, n, whole, call, fmt, given):
+        # what load and load_raw share: `call(handle, buffer)` is the library's load of a device buffer of n samples -- x,
+        # or what the blanker made of it
         h = self._device_tuner(n)
+        if self._blanker is not None:
+            x = self._blank(x, n, fmt, self._is_upload(given, x))
         if self._handle_fine is not self._fine:        # a lane that follows the base tuner's retune, on its own stream
             self._apply_fine(h, self._fine)
         if self._handle_iq is not self._iq_balance:    # ... and its set_iq_balance
@@ -234,11 +248,11 @@ class Tuner(Injector):
         if whole and self._shard is not None:
             hip.check(self._lib.rcfm_tuner_shard(h, 0, len(self._bounds)))
             try:
-                hip.check(call(h))
+                hip.check(call(h, x))
             finally:      # a failed load must not leave the handle sharded to every channel
                 hip.check(self._lib.rcfm_tuner_shard(h, self._shard[0], self._shard[1]))
         else:
-            hip.check(call(h))
+            hip.check(call(h, x))
         self._input = x            # keeps the buffer alive until the FFT has consumed it
         self._loaded_size = n
 
@@ -501,6 +515,58 @@ class Tuner(Injector):
         mode, beta, notch = self._iq_balance if self._iq_balance is not None else (hip.RCFM_IQ_BALANCE_OFF, 0j, 0)
         hip.check(self._lib.rcfm_tuner_set_iq_balance(handle, mode, beta.real, beta.imag, notch))
         self._handle_iq = self._iq_balance
+
+    # ---- noise blanker (rcfm_blanker_run ahead of the load; no reference counterpart) -----------------------------------
+
+    def set_blanker(self, blanker=None, in_place=False):
+        """Impulse noise taken out of every buffer from now on: with a ``radiocore.NoiseBlanker``, ``load`` / ``load_raw``
+        (and ``Lanes.submit``) queue the blanker ahead of the wideband FFT -- and so ahead of the IQ balance, whose estimate
+        sees the cleaned buffer -- on the caller's stream and without a host synchronisation; ``blanker_stats()`` tells what
+        it did.  A host array is uploaded into a device tensor of its own anyway and is blanked in place there.  A caller's
+        device tensor is left untouched: the tuner blanks it into a scratch tensor of the buffer's format and size, allocated
+        by the first such load and kept (8 bytes per sample for complex64: 1.92 GB for a buffer of 2.4e8 samples) -- unless
+        ``in_place=True``, which blanks the caller's tensor itself and needs no scratch.  ``shard``, ``whole=True``, attached
+        spectra and windows are unaffected: the blanker acts on the input buffer, which every load has whole.  ``None``
+        (the default) turns it off: nothing more is launched than before.  Each device tuner (each lane) keeps a blanker
+        handle, and so the scratch of a run, of its own.  ValueError for anything but a NoiseBlanker, or one whose hold and
+        ramp exceed 1024 samples of this tuner's buffers."""
+        if blanker is None:
+            self._blanker = None
+            self._blank_handles = {}
+            self._blank_scratch = None
+            return
+        if not hasattr(blanker, "geometry") or not hasattr(blanker, "_create"):
+            raise ValueError("set_blanker takes a radiocore.NoiseBlanker")
+        if self._input_bandwidth:
+            blanker.geometry(int(self._input_bandwidth))
+        self._blanker = (blanker, bool(in_place))
+
+    def blanker_stats(self):
+        """``(hits, blanked)`` of this tuner's last ``load`` / ``load_raw`` with a blanker set: the number of samples over
+        the threshold and the number whose gain was below 1.  Waits for the device."""
+        if self._blank_counts is None:
+            raise RuntimeError("blanker_stats: no load with a blanker set (set_blanker) yet")
+        c = hip.to_host(self._blank_counts)
+        return int(c[0]), int(c[1])
+
+    def _blank(self, x, n, fmt, upload):
+        # ahead of the load on the same stream: x itself where it is this load's own upload (or in_place), else the scratch
+        blanker, in_place = self._blanker
+        blanker.geometry(n)
+        ent = self._blank_handles.get(n)
+        if ent is None or ent[0] is not blanker:
+            ent = self._blank_handles[n] = (blanker, blanker._create(n))
+        dst = x
+        if not (upload or in_place):
+            s = self._blank_scratch
+            if s is None or s.dtype != x.dtype or tuple(s.shape) != tuple(x.shape):
+                s = self._blank_scratch = hip.empty(tuple(x.shape), x.dtype)
+            dst = s
+        if self._blank_counts is None:
+            self._blank_counts = hip.empty((2,), self._torch.int64)
+        hip.check(self._lib.rcfm_blanker_run(ent[1].value, fmt, n, hip.ptr(x), hip.ptr(dst), hip.ptr(self._blank_counts),
+                                             hip.stream()))
+        return dst
 
     def set_squelch(self, threshold=None):
         """Mute what is below a level: from now on ``run_all`` / ``run_each`` (and ``Lanes.submit``) compare every
@@ -1008,6 +1074,8 @@ class Tuner(Injector):
             self._afilt, self._afilt_dev, self._afilt_ready = base._afilt, None, None
         self._afilt_handles = base._afilt_handles
         self._iq_balance = base._iq_balance                # ... its IQ balance (the next load applies it; per buffer, nothing to fence)
+        if self._blanker is not base._blanker:             # ... and its noise blanker, with a handle and scratch of this lane's own
+            self._blanker, self._blank_handles, self._blank_scratch = base._blanker, {}, None
         if self._fine is not base._fine:                   # ... and its fine-tune (a new object per retune): the next load applies it
             self._fine, self._abi_arrays = base._fine, None
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
