@@ -12,10 +12,17 @@ Measured (`pipelined` blocks of profiles/r04_i_bench.json, same box as the one-l
 tiles per CU) -11 %.  Costs one more spectrum and workspace set per lane (cfg4: 14 GB).
 """
 
+from collections import namedtuple
+
 from radiocore._internal import hip
 from radiocore.tools.tuner import Tuner
 
 __all__ = ["Lanes"]
+
+
+# One submitted buffer until result() collects it: the event behind its last launch, the event behind its load (= the last
+# reader of the input), the Tuner's run record (audio blocks, squelch masks or None, tone powers or None), submit's `each`.
+_Pending = namedtuple("_Pending", "end loaded run each")
 
 
 class Lanes:
@@ -43,8 +50,7 @@ class Lanes:
         self._tuners = [tuner] + [tuner._lane_clone() for _ in range(depth - 1)]
         self._streams = [self._torch.cuda.Stream() for _ in range(depth)]
         self._next = 0
-        self._pending = {}          # ticket -> (end event, audio tensor, event behind the load = last reader of the input,
-                                    #            the squelch's device masks or None, the tone bank's device (P, E) or None)
+        self._pending = {}          # ticket -> _Pending
         self._spans = {}            # timing=True: ticket -> (start event, end event)
 
     @property
@@ -74,9 +80,9 @@ class Lanes:
             start = self._event(st) if self._timing else None
             (t.load_raw if raw else t.load)(input_signal)
             loaded = self._event(st)            # the wideband FFT is the LAST reader of the input buffer
-            audio = t._run_each_device() if each else t._run_all_device(chunk)
+            run = t._run_each_device() if each else t._run_all_device(chunk)
             ev = self._event(st)
-        self._pending[ticket] = (ev, audio, loaded, t._open, t._tone_out)
+        self._pending[ticket] = _Pending(ev, loaded, run, each)
         if self._timing:
             self._spans[ticket] = (start, ev)
         return ticket
@@ -99,28 +105,27 @@ class Lanes:
         open_mask=True: ``(audio, mask)`` with the squelch's numpy bool [C] of that buffer (Tuner.open_mask; None when
         the buffer was submitted with squelch off).  tones=True: the tone bank's ``(P, E)`` of that buffer
         (Tuner.tone_power; None when it was submitted without a bank) comes last in the tuple."""
-        ev, audio, _, masks, tone_out = self._pending.pop(ticket)
+        entry = self._pending.pop(ticket)
+        run = entry.run
         device_output = self._base._cuda and not numpy_output
         if device_output:
             cur = self._torch.cuda.current_stream()
-            cur.wait_event(ev)                                 # stream-ordered hand-over, no host wait
-            for a in ([b[2] for b in audio] if isinstance(audio, list) else [audio]):
+            cur.wait_event(entry.end)                          # stream-ordered hand-over, no host wait
+            for _, _, a in run.blocks:
                 a.record_stream(cur)
         else:
-            ev.synchronize()
-        if isinstance(audio, list):                            # submit(each=True): Tuner.run_each's list
-            out = self._base._each_result(audio, device_output)
-        else:
-            out = audio if device_output else hip.to_host(audio)
+            entry.end.synchronize()
+        out = self._base._each_result(run.blocks, device_output) if entry.each else \
+            self._base._result(run.blocks[0][2], device_output)
         extra = []
         if open_mask:
-            extra.append(Tuner._mask_result(masks) if masks is not None else None)
+            extra.append(Tuner._mask_result(run.masks) if run.masks is not None else None)
         if tones:
-            if device_output and tone_out is not None:
-                for p, e in tone_out:
+            if device_output and run.tones is not None:
+                for p, e in run.tones:
                     p.record_stream(cur)
                     e.record_stream(cur)
-            extra.append(self._base._tone_result(tone_out, device_output) if tone_out is not None else None)
+            extra.append(self._base._tone_result(run.tones, device_output) if run.tones is not None else None)
         return (out, *extra) if extra else out
 
     def hold_current_stream(self, ticket: int):
@@ -136,9 +141,9 @@ class Lanes:
         run the recipe from a stream that gets a queue of its own, e.g. ``torch.cuda.Stream(priority=-1)`` (each
         priority has its own queues) made current in a process whose streams do not already fill that priority's
         queues (tests/test_hip_lanes.py)."""
-        self._torch.cuda.current_stream().wait_event(self._pending[ticket][2])
+        self._torch.cuda.current_stream().wait_event(self._pending[ticket].loaded)
 
     def drain(self):
         """Wait for everything submitted so far (results stay collectable)."""
         for entry in self._pending.values():
-            entry[0].synchronize()
+            entry.end.synchronize()

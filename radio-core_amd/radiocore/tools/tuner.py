@@ -6,6 +6,7 @@ wideband FFT, the per-channel bin gather / weight / inverse FFT and (for
 """
 
 import ctypes
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import List
 
@@ -20,6 +21,10 @@ _KINDS = {"FM": hip.RCFM_FM, "MFM": hip.RCFM_MFM, "WBFM": hip.RCFM_WBFM, "AM": h
           "USB": hip.RCFM_USB, "LSB": hip.RCFM_LSB}
 _STATELESS = (hip.RCFM_FM, hip.RCFM_AM, hip.RCFM_USB, hip.RCFM_LSB)    # kinds without de-emphasis state: nothing to bind or fence
                                                                        # (unless AM / USB / LSB carry an AGC: its state is bound and fenced)
+_DEFAULT_OPTIONS = (True, True, True, 1, True)                         # set_kernel_options: lds_chain, fused_tiles, phase_link, narrow_tiles, ssb_direct
+# What one run_all / run_each queued, on the device, one entry per launch group: blocks [(n, ch, audio [n, A, ch])]; masks, the
+# squelch's uint8 [n], or None (no squelch was set, or nothing was gated); tones, the bank's (P, E), or None (no bank was set).
+_Run = namedtuple("_Run", "blocks masks tones", defaults=(None, None, None))
 
 
 def _key_agc(key):
@@ -69,29 +74,28 @@ class Tuner(Injector):
         # (`_version`): load / run / run_all do no per-channel Python work in the steady state.
         self._version = 0
         self._lo = self._hi = self._bw_sum = None     # running min / max / sum of _recalculate
-        self._abi_arrays = None    # (version, rolls, bws) as ctypes arrays
+        self._abi_arrays = None    # (version, rolls, bws, the _fine the rolls include) as ctypes arrays
         self._plan = None          # (version, shard) -> run_all / run_each launch plan
         self._uniform = (None, None)   # (version, the one geometry all channels share or None)
         self._state_owner = {}     # (kind, C, B, A, tau) -> the batched handle whose buffer holds that geometry's state
         self._bound_version = {}   # batched key -> channel-list version its demodulators were bound at
         self._state_fence = False  # Lanes: this tuner's batched handles run on several streams (RCFM_OPT_STATE_FENCE)
-        self._squelch = None       # set_squelch: None (off) or float32 thresholds, 0-d (every channel) or [len(channels())]
-        self._squelch_dev = None   # (channel-list version, device float32 [C]): rebuilt when either changes
-        self._open = None          # device uint8 masks of the last run_all / run_each, one per launch group
-        self._fine = None          # retune: None or int64 [len(channels())] bins each channel was moved up (a new object per retune)
-        self._handle_fine = None   # the _fine the device handle's rolls were last set from
+        self._is_lane = False      # _lane_clone: a second device tuner over another Tuner's channels and states
+        self._kernel_options = _DEFAULT_OPTIONS
         self._taps = {}            # (B, R, f, taps) -> (channels it holds, batched subcarrier handle) of subcarrier()
-        self._iq_balance = None    # set_iq_balance: None (off) or (mode, beta, dc_notch) (a new object per setting)
-        self._handle_iq = None     # the _iq_balance the device handle was last set to
-        self._tones = None         # set_tones: None (off) or (bank, want int32 [C] or None, ratio float32 [C] or None) (a new object per setting)
-        self._tones_dev = None     # (channel-list version, device int32 [C], device float32 [C]) of a tone squelch
-        self._tone_out = None      # device (P, E) of the last run_all / run_each, one pair per launch group
-        self._tones_ready = None   # (launch-plan key, the _tones it was checked for): the bank fits every group's audio length
-        self._afilt = None         # set_audio_filter: None (off) or (AudioFilter, uint8 [C] or None) (a new object per setting)
-        self._afilt_dev = None     # (channel-list version, device uint8 [C]) of the filter's channel selection
+        # The settings: host values, replaced by their set_* and never changed in place, so that a lane follows by identity.
+        self._squelch = None       # set_squelch: None (off) or float32 thresholds, 0-d (every channel) or [len(channels())]
+        self._fine = None          # retune: None or int64 [len(channels())] bins each channel was moved up
+        self._iq_balance = None    # set_iq_balance: None (off) or (mode, beta, dc_notch)
+        self._tones = None         # set_tones: None (off) or (bank, want int32 [C] or None, ratio float32 [C] or None)
+        self._afilt = None         # set_audio_filter: None (off) or (AudioFilter, uint8 [C] or None)
+        self._blanker = None       # set_blanker: None (off) or (NoiseBlanker, in_place)
+        # What is made FROM a setting -- device copies, "fits this launch plan", what the device handle was last told -- is
+        # looked up with what it is made from (_derived) and made again when that differs: nothing invalidates it by hand.
+        self._built = {}           # name -> (setting, channel-list version / launch-plan key / handle key, what was made)
+        self._last = _Run()        # masks and tone powers of the last run_all / run_each (not its audio: the caller's)
+        # Device state that is no copy of a setting: the filter's, shared by a lane, and the blanker's, each lane's own.
         self._afilt_handles = {}   # (legs, A) -> (channels, AudioFilter, librcfm handle): the filter's states, by channel index
-        self._afilt_ready = None   # (launch-plan key, the _afilt it was checked for): the filter has a design for every group's audio rate
-        self._blanker = None       # set_blanker: None (off) or (NoiseBlanker, in_place) (a new object per setting)
         self._blank_handles = {}   # buffer length n -> (the NoiseBlanker it was made by, librcfm handle): this device tuner's own scratch
         self._blank_scratch = None # the blanked copy of a caller's device tensor (buffer's dtype and size; allocated by the first such load)
         self._blank_counts = None  # device int64 [2] of the last load with a blanker: hits, samples with gain below 1
@@ -162,30 +166,55 @@ class Tuner(Injector):
         mean_bandwidth //= len(self._bounds)
         self._input_bandwidth += (self._input_bandwidth * -1) % mean_bandwidth
 
+    def _derived(self, name, setting, key, make):
+        """What `make()` made for `name` from `setting` (compared by identity) under `key` (channel-list version, launch-plan
+        key or device handle's key, compared by value): made now unless just that is held.  A `make` that raises keeps nothing."""
+        held = self._built.get(name)
+        if held is None or held[0] is not setting or held[1] != key:
+            held = self._built[name] = (setting, key, make())
+        return held[2]
+
+    def _per_channel(self, a, what, scalar=True):
+        """The array `a` -- one value per channel, or (scalar=True) one for all -- or ValueError: `what` and the count."""
+        C = len(self._bounds)
+        if a.ndim > 1 or (a.ndim == 0 and not scalar) or (a.ndim == 1 and a.shape[0] != C):
+            raise ValueError("%s (%d)" % (what, C))
+        return a
+
+    def _out(self, tensor, numpy_output):
+        """A device tensor as the caller asked for it: left on the device only by a cuda=True tuner with numpy_output=False."""
+        return self._result(tensor, self._cuda and not numpy_output)
+
     # ---- device side ---------------------------------------------------------
 
     def _device_tuner(self, n):
         # rolls depend on the channel list only (input_frequency is recomputed by add_channel, never by
-        # request_bandwidth): the handle is keyed by (n, _version) and the O(C) lists are built once per version
+        # request_bandwidth) and on the fine-tune: the handle is keyed by (n, _version) and the O(C) lists are built once
+        # per version and retune
         key = (n, self._version)
         if key != self._handle_key:
-            if self._abi_arrays is None or self._abi_arrays[0] != self._version:
+            held = self._abi_arrays
+            if held is None or held[0] != self._version or held[3] is not self._fine:
                 bws = [int(ch.bandwidth) for ch in self._bounds]
-                self._abi_arrays = (self._version, self._rolls(self._fine), (ctypes.c_int32 * len(bws))(*bws))
-            _, roll_a, bw_a = self._abi_arrays
+                held = self._abi_arrays = (self._version, self._rolls(self._fine), (ctypes.c_int32 * len(bws))(*bws), self._fine)
             h = ctypes.c_void_p()
             with hip.bound(self._arena):
-                hip.check(self._lib.rcfm_tuner_create(n, len(self._bounds), roll_a, bw_a, ctypes.byref(h)))
+                hip.check(self._lib.rcfm_tuner_create(n, len(self._bounds), held[1], held[2], ctypes.byref(h)))
             self._handle = hip.Handle(h, self._lib.rcfm_tuner_destroy)
             self._handle_key = key
-            self._handle_fine = self._fine
             self._loaded_size = None
-            self._handle_iq = None
+            self._built["fine"] = (self._fine, key, None)      # what a new handle knows: the rolls it was made with ...
+            self._built["iq"] = (None, key, None)              # ... and no IQ balance
             if self._shard is not None:
                 hip.check(self._lib.rcfm_tuner_shard(h, self._shard[0], self._shard[1]))
-            if self._iq_balance is not None:
-                self._apply_iq_balance(h)
+            self._follow(h)
         return self._handle.value
+
+    def _follow(self, h):
+        # the device handle h is told of a retune and a set_iq_balance it has not seen (one that exists is told by those calls
+        # themselves): a new handle, and a lane's with the lane's next load, on its own stream (per buffer, nothing to fence)
+        self._derived("fine", self._fine, self._handle_key, lambda: self._retune(h, self._fine))
+        self._derived("iq", self._iq_balance, self._handle_key, lambda: self._apply_iq_balance(h))
 
     def _rolls(self, fine):
         # roll[c] = int(f_in - f_c) (tuner.py:152) minus the bins the channel was moved up by retune
@@ -194,9 +223,8 @@ class Tuner(Injector):
             rolls = [r - int(k) for r, k in zip(rolls, fine)]
         return (ctypes.c_int64 * len(rolls))(*rolls)
 
-    def _apply_fine(self, handle, fine):
+    def _retune(self, handle, fine):
         hip.check(self._lib.rcfm_tuner_retune(handle, 0, len(self._bounds), self._rolls(fine), hip.stream()))
-        self._handle_fine = fine
 
     def shard(self, first, count):
         """Multi-GPU only (no reference counterpart): this process will run channels
@@ -241,10 +269,7 @@ class Tuner(Injector):
         h = self._device_tuner(n)
         if self._blanker is not None:
             x = self._blank(x, n, fmt, self._is_upload(given, x))
-        if self._handle_fine is not self._fine:        # a lane that follows the base tuner's retune, on its own stream
-            self._apply_fine(h, self._fine)
-        if self._handle_iq is not self._iq_balance:    # ... and its set_iq_balance
-            self._apply_iq_balance(h)
+        self._follow(h)
         if whole and self._shard is not None:
             hip.check(self._lib.rcfm_tuner_shard(h, 0, len(self._bounds)))
             try:
@@ -361,7 +386,7 @@ class Tuner(Injector):
         _, first, count = self._launch_plan()
         power = hip.empty((count,), self._torch.float32)
         hip.check(self._lib.rcfm_tuner_levels(handle, first, count, hip.ptr(power), hip.stream()))
-        return self._result(power, self._cuda and not numpy_output)
+        return self._out(power, numpy_output)
 
     # ---- carrier estimates and live retune (rcfm_tuner_carriers / rcfm_tuner_retune; no reference counterpart) --------
 
@@ -377,7 +402,7 @@ class Tuner(Injector):
         t = self._torch
         out = [hip.empty((count,), dt) for dt in (t.int32, t.float32, t.float32, t.float32)]
         hip.check(self._lib.rcfm_tuner_carriers(handle, first, count, float(gate), *[hip.ptr(o) for o in out], hip.stream()))
-        return tuple(self._result(o, self._cuda and not numpy_output) for o in out)
+        return tuple(self._out(o, numpy_output) for o in out)
 
     def retune(self, offsets):
         """Move channel c up by ``offsets[c]`` bins (Hz with one-second buffers; a scalar moves every channel), on top of
@@ -390,14 +415,12 @@ class Tuner(Injector):
         if a.dtype.kind not in "iu":
             if a.dtype.kind != "f" or not np.all(a == np.round(a)):
                 raise ValueError("retune offsets are whole numbers of bins")
-        C = len(self._bounds)
-        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != C):
-            raise ValueError("retune offsets: a scalar or one per channel (%d)" % C)
-        fine = self.fine_tune() + np.broadcast_to(a, (C,)).astype(np.int64)      # (a new object per retune: lanes compare by identity)
+        a = self._per_channel(a, "retune offsets: a scalar or one per channel")
+        fine = self.fine_tune() + np.broadcast_to(a, (len(self._bounds),)).astype(np.int64)    # (a new object per retune)
         if self._handle is not None and self._handle_key[1] == self._version:
-            self._apply_fine(self._handle.value, fine)
+            self._retune(self._handle.value, fine)               # (refused: the fine-tune in force stays)
+            self._built["fine"] = (fine, self._handle_key, None)
         self._fine = fine
-        self._abi_arrays = None
 
     def fine_tune(self):
         """int64 [len(channels())]: the bins every channel has been moved up by ``retune`` since the channel list last changed."""
@@ -429,7 +452,7 @@ class Tuner(Injector):
             self._taps[key] = held = (len(self._bounds), tap._create(len(self._bounds), 0))
         out = hip.empty((count, tap._output_size), self._torch.complex64)
         hip.check(self._lib.rcfm_pipeline_subcarrier(handle, held[1].value, first, count, hip.ptr(out), hip.stream()))
-        return self._result(out, self._cuda and not numpy_output)
+        return self._out(out, numpy_output)
 
     def power_spectrum(self, cells, f_lo=None, f_hi=None, peak=False, numpy_output: bool = True):
         """What the band looks like between and around the channels (rcfm_tuner_power_spectrum; no reference
@@ -450,7 +473,7 @@ class Tuner(Injector):
         out = [hip.empty((cells,), self._torch.float32) for _ in range(2 if peak else 1)]
         hip.check(self._lib.rcfm_tuner_power_spectrum(handle, s0, L, cells, hip.ptr(out[0]), hip.ptr(out[1]) if peak else None,
                                                       hip.stream()))
-        out = [self._result(o, self._cuda and not numpy_output) for o in out]
+        out = [self._out(o, numpy_output) for o in out]
         return (out[0], out[1]) if peak else out[0]
 
     # ---- IQ balance (rcfm_tuner_iq_estimate / _iq_correct / _set_iq_balance; no reference counterpart) -----------------
@@ -510,11 +533,11 @@ class Tuner(Injector):
         self._iq_balance = setting
         if self._handle is not None and self._handle_key[1] == self._version:
             self._apply_iq_balance(self._handle.value)
+            self._built["iq"] = (setting, self._handle_key, None)
 
     def _apply_iq_balance(self, handle):
         mode, beta, notch = self._iq_balance if self._iq_balance is not None else (hip.RCFM_IQ_BALANCE_OFF, 0j, 0)
         hip.check(self._lib.rcfm_tuner_set_iq_balance(handle, mode, beta.real, beta.imag, notch))
-        self._handle_iq = self._iq_balance
 
     # ---- noise blanker (rcfm_blanker_run ahead of the load; no reference counterpart) -----------------------------------
 
@@ -576,36 +599,20 @@ class Tuner(Injector):
         demodulators still run on every channel: the de-emphasis state advances as without squelch.  A NaN threshold
         keeps a channel closed.  ``None`` (the default) turns squelch off: nothing more is launched than before.
         ``squelch.threshold_over_floor`` derives thresholds from a ``levels()`` pass."""
-        if threshold is None:
-            self._squelch = None
-        else:
-            a = np.array(threshold, dtype=np.float32)      # (a copy: a new object per setting, lanes compare by identity)
-            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != len(self._bounds)):
-                raise ValueError("squelch thresholds: a scalar or one per channel (%d)" % len(self._bounds))
-            self._squelch = a
-        self._squelch_dev = None
-        self._open = None
+        self._squelch = None if threshold is None else self._per_channel(        # (np.array: a copy, a new object per setting)
+            np.array(threshold, dtype=np.float32), "squelch thresholds: a scalar or one per channel")
+        self._last = self._last._replace(masks=None)
 
     def open_mask(self):
         """numpy bool [count]: which channels the squelch -- the level squelch, the tone squelch, or both combined -- left
         open in this tuner's last ``run_all`` / ``run_each``."""
-        if self._open is None:
+        if self._last.masks is None:
             raise RuntimeError("open_mask: no run_all / run_each with squelch set (set_squelch) yet")
-        return self._mask_result(self._open)
+        return self._mask_result(self._last.masks)
 
     @staticmethod
     def _mask_result(masks):
         return np.concatenate([hip.to_host(m) for m in masks]).astype(bool) if masks else np.zeros(0, bool)
-
-    def _thresholds(self):
-        if self._squelch_dev is None or self._squelch_dev[0] != self._version:
-            a = self._squelch
-            if a.ndim == 1 and a.shape[0] != len(self._bounds):
-                raise ValueError("squelch thresholds were set for %d channels, the tuner has %d"
-                                 % (a.shape[0], len(self._bounds)))
-            full = np.ascontiguousarray(np.broadcast_to(a, (len(self._bounds),)))
-            self._squelch_dev = (self._version, hip.to_device(full, self._torch.float32))
-        return self._squelch_dev[1]
 
     # ---- tone bank and tone squelch (rcfm_tone_bank_run / rcfm_tone_score; no reference counterpart) ---------------------
 
@@ -638,38 +645,32 @@ class Tuner(Injector):
                     w = np.array([bank.index(v.item() if isinstance(v, np.generic) else v) for v in want], dtype=np.int32)
                 else:
                     w = np.full(C, bank.index(want), dtype=np.int32)
-                r = np.array(ratio, dtype=np.float32)
-                if r.ndim > 1 or (r.ndim == 1 and r.shape[0] != C):
-                    raise ValueError("tone ratios: a scalar or one per channel (%d)" % C)
+                r = self._per_channel(np.array(ratio, dtype=np.float32), "tone ratios: a scalar or one per channel")
                 r = np.array(np.broadcast_to(r, (C,)))           # (a copy: writable, contiguous)
             setting = (bank, w, r)
             self._fit_tones(setting)               # refused here, with the old setting still in force
             self._tones = setting
-        self._tones_dev = None
-        self._tone_out = None
-        self._open = None
+        self._last = _Run()
+
+    def _fit(self, name, setting, check):
+        """``check(the audio lengths of the launch plan's groups, ascending)`` once per (channel list, shard, setting): what
+        does not fit these channels raises there, before a run has advanced any state."""
+        if setting is not None and self._bounds:
+            groups, _, _ = self._launch_plan()
+            self._derived(name, setting, self._plan[0], lambda: check(sorted({g[4] for g in groups if g[2] is not None})))
 
     def _fit_tones(self, setting):
         """The bank's device handle for the audio length of every group of the launch plan, made now: whatever is wrong
-        with the bank for these channels raises here, before a run has advanced any demodulator state.  Once per
-        (channel list, shard, setting)."""
-        if not self._bounds:
-            return
-        groups, first, count = self._launch_plan()
-        key = (self._plan[0], setting)
-        if self._tones_ready is not None and self._tones_ready[0] == key[0] and self._tones_ready[1] is setting:
-            return
-        for A in sorted({g[4] for g in groups if g[2] is not None}):
-            setting[0]._handle(A)
-        self._tones_ready = key
+        with the bank for these channels raises here, before a run has advanced any demodulator state."""
+        self._fit("tones fit", setting, lambda lengths: [setting[0]._handle(A) for A in lengths])
 
     def tone_power(self, numpy_output: bool = True):
         """``(P [count, F, K], E [count, F])`` of this tuner's last ``run_all`` / ``run_each`` with a tone bank set: the
         power at each tone and the total power of every frame of every channel.  (``run_each`` over groups whose audio
         lengths give different frame counts: a list with one such pair per group.)"""
-        if self._tone_out is None:
+        if self._last.tones is None:
             raise RuntimeError("tone_power: no run_all / run_each with a tone bank set (set_tones) yet")
-        return self._tone_result(self._tone_out, self._cuda and not numpy_output)
+        return self._tone_result(self._last.tones, self._cuda and not numpy_output)
 
     def _tone_result(self, pairs, device_output):
         t = self._torch
@@ -682,11 +683,12 @@ class Tuner(Injector):
     def _tone_squelch(self, first, count, audio, tones, gate):
         # behind the group's tone bank (and level squelch): the wanted tone's best share, then mask + zero fill on it
         bank, want, ratio = self._tones
-        if self._tones_dev is None or self._tones_dev[0] != self._version:
+
+        def upload():
             if want.shape[0] != len(self._bounds):
                 raise ValueError("wanted tones were set for %d channels, the tuner has %d" % (want.shape[0], len(self._bounds)))
-            self._tones_dev = (self._version, hip.to_device(want, self._torch.int32), hip.to_device(ratio, self._torch.float32))
-        _, want_dev, ratio_dev = self._tones_dev
+            return hip.to_device(want, self._torch.int32), hip.to_device(ratio, self._torch.float32)
+        want_dev, ratio_dev = self._derived("tone squelch", self._tones, self._version, upload)
         P, E = tones
         score = hip.empty((count,), self._torch.float32)
         mask = hip.empty((count,), self._torch.uint8)
@@ -722,29 +724,23 @@ class Tuner(Injector):
                 raise ValueError("set_audio_filter takes a radiocore.AudioFilter")
             sel = None
             if channels is not None:
-                sel = np.array(channels, dtype=bool).astype(np.uint8)
-                if sel.ndim != 1 or sel.shape[0] != len(self._bounds):
-                    raise ValueError("filtered channels: one bool per channel (%d)" % len(self._bounds))
+                sel = self._per_channel(np.array(channels, dtype=bool).astype(np.uint8),
+                                        "filtered channels: one bool per channel", scalar=False)
             setting = (filt, sel)
             self._fit_afilt(setting)               # refused here, with the old setting still in force
             if self._afilt is None or self._afilt[0] is not filt:
                 self._afilt_handles.clear()        # another filter: its states start at rest
             self._afilt = setting
-        self._afilt_dev = None
 
     def _fit_afilt(self, setting):
         """The filter's design for the audio rate of every group of the launch plan, and the selection's length: whatever
-        is wrong raises here, before a run has advanced any state.  Once per (channel list, shard, setting)."""
-        if not self._bounds:
-            return
-        groups, first, count = self._launch_plan()
-        if self._afilt_ready is not None and self._afilt_ready[0] == self._plan[0] and self._afilt_ready[1] is setting:
-            return
-        if setting[1] is not None and setting[1].shape[0] != len(self._bounds):
-            raise ValueError("filtered channels were set for %d channels, the tuner has %d" % (setting[1].shape[0], len(self._bounds)))
-        for A in sorted({g[4] for g in groups if g[2] is not None}):
-            setting[0].sections(A)
-        self._afilt_ready = (self._plan[0], setting)
+        is wrong raises here, before a run has advanced any state."""
+        def check(lengths):
+            if setting[1] is not None and setting[1].shape[0] != len(self._bounds):
+                raise ValueError("filtered channels were set for %d channels, the tuner has %d" % (setting[1].shape[0], len(self._bounds)))
+            for A in lengths:
+                setting[0].sections(A)
+        self._fit("filter fit", setting, check)
 
     def _afilt_handle(self, ch, A):
         # one handle per (legs, audio rate), sized for all channels: its state slots are addressed by channel index, so
@@ -770,9 +766,8 @@ class Tuner(Injector):
         # behind the group's tone bank on the same stream, in place
         sel = None
         if self._afilt[1] is not None:
-            if self._afilt_dev is None or self._afilt_dev[0] != self._version:
-                self._afilt_dev = (self._version, hip.to_device(self._afilt[1]))
-            sel = ctypes.c_void_p(self._afilt_dev[1].data_ptr() + first)
+            dev = self._derived("filter selection", self._afilt, self._version, lambda: hip.to_device(self._afilt[1]))
+            sel = ctypes.c_void_p(dev.data_ptr() + first)
         A, ch = int(audio.shape[1]), int(audio.shape[2])
         hip.check(self._lib.rcfm_audio_filter_run(self._afilt_handle(ch, A), first, count, A, hip.ptr(audio), hip.ptr(audio),
                                                   sel, hip.stream()))
@@ -793,7 +788,14 @@ class Tuner(Injector):
 
     def _squelch_group(self, handle, first, count, audio):
         # behind the group's rcfm_pipeline_run on the same stream: levels of its channels, then mask + zero fill
-        thr = self._thresholds()
+        def upload():
+            a = self._squelch
+            if a.ndim == 1 and a.shape[0] != len(self._bounds):
+                raise ValueError("squelch thresholds were set for %d channels, the tuner has %d"
+                                 % (a.shape[0], len(self._bounds)))
+            full = np.ascontiguousarray(np.broadcast_to(a, (len(self._bounds),)))
+            return hip.to_device(full, self._torch.float32)
+        thr = self._derived("squelch", self._squelch, self._version, upload)
         power = hip.empty((count,), self._torch.float32)
         mask = hip.empty((count,), self._torch.uint8)
         s = hip.stream()
@@ -836,28 +838,42 @@ class Tuner(Injector):
         After ``shard(first, count)`` only that range is run (its spectrum rows are all ``load``
         kept) and the result is [count, A, ch] -- the block sharding.gather_audio expects.
         """
-        return self._result(self._run_all_device(chunk), self._cuda and not numpy_output)
+        return self._out(self._run_all_device(chunk).blocks[0][2], numpy_output)
 
     def _run_all_device(self, chunk=0):
-        # run_all's launches on the current stream; the device tensor they fill (Lanes collects it later)
+        # run_all's launches on the current stream: ONE group, the shard's range (launched even when empty) with the geometry
+        # all channels share; the _Run they fill (Lanes collects it later)
         handle = self._ready()
         _, first, count = self._launch_plan()
         geo = self._plan_uniform()     # ALL channels of the tuner, not only the shard's
         if geo is None:
             raise ValueError("run_all needs one demodulator class and geometry for all channels")
-        kind, B, A, tau = geo[:4]
-        ch = 2 if kind == hip.RCFM_WBFM else 1
-        if self._tones is not None:
-            self._fit_tones(self._tones)
-        if self._afilt is not None:
-            self._fit_afilt(self._afilt)
-        audio = hip.empty((count, A, ch), self._torch.float32)
-        hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk, *geo[4:]), first, count,
-                                              hip.ptr(audio), hip.stream()))
-        tones, mask = self._gates(handle, first, count, audio) if count else (None, None)
-        self._open = [mask] if mask is not None else None
-        self._tone_out = [tones] if tones is not None else None
-        return audio
+        return self._run_groups(handle, [(first, count) + geo], chunk)
+
+    def _run_groups(self, handle, groups, chunk=0):
+        """The launches of run_all / run_each on the current stream: per group (first, count, kind, B, A, tau[, agc]) of like
+        channels its audio, rcfm_pipeline_run and what follows it (_gates); a tone bank or filter that does not fit is refused
+        before the first launch.  Returns the _Run and keeps its masks and tone powers for open_mask() / tone_power()."""
+        self._fit_tones(self._tones)
+        self._fit_afilt(self._afilt)
+        gated = self._squelch is not None or (self._tones is not None and self._tones[1] is not None)
+        run = _Run([], [] if gated else None, [] if self._tones is not None else None)
+        for first, count, kind, B, A, tau, *agc in groups:
+            ch = 2 if kind == hip.RCFM_WBFM else 1
+            audio = hip.empty((count, A, ch), self._torch.float32)
+            hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk, *agc), first, count,
+                                                  hip.ptr(audio), hip.stream()))
+            run.blocks.append((count, ch, audio))
+            if not count:                  # run_all of an empty shard: nothing to gate, and nothing to ask for afterwards
+                run = run._replace(masks=None, tones=None)
+                continue
+            tones, mask = self._gates(handle, first, count, audio)
+            if run.masks is not None:
+                run.masks.append(mask)
+            if run.tones is not None:
+                run.tones.append(tones)
+        self._last = _Run(None, run.masks, run.tones)
+        return run
 
     def run_all_packed(self, pcm, numpy_output: bool = True, chunk: int = 0, drain=None):
         """``run_all`` for a publisher (rcfm_audio_pack; no reference counterpart): the audio of the OPEN channels only,
@@ -884,9 +900,10 @@ class Tuner(Injector):
                                  % (drain.rows, drain.row_shape, drain.dtype, count, shape, pcm.dtype))
         if drain is not None:
             packed, index, n_open = drain._begin()         # ... and so is a drain with every slot in flight
-        audio = self._run_all_device(chunk)
+        run = self._run_all_device(chunk)
+        audio = run.blocks[0][2]
         row = int(audio.shape[1]) * int(audio.shape[2])
-        mask = self._open[0] if self._open else None
+        mask = run.masks[0] if run.masks else None
         args = (hip.ptr(audio), hip.ptr(mask) if mask is not None else None, count, row, pcm.format, pcm.gain)
         if drain is not None:
             hip.check(self._lib.rcfm_audio_pack(*args, packed, index, n_open, hip.stream()))
@@ -920,35 +937,15 @@ class Tuner(Injector):
         de-emphasis state is the tuner's, per channel, as in ``run_all``.  After ``shard(first, count)`` the list
         covers that range only.
         """
-        return self._each_result(self._run_each_device(), self._cuda and not numpy_output)
+        return self._each_result(self._run_each_device().blocks, self._cuda and not numpy_output)
 
     def _run_each_device(self):
-        # run_each's launches on the current stream; [(n, ch, device tensor [n, A, ch])] per group of like channels
+        # run_each's launches on the current stream: the launch plan's groups of like channels; the _Run they fill
         handle = self._ready()
         groups, first, count = self._launch_plan()
-        blocks = []
-        masks = [] if self._squelch is not None or (self._tones is not None and self._tones[1] is not None) else None
-        tone_out = [] if self._tones is not None else None
-        if self._tones is not None:
-            self._fit_tones(self._tones)
-        if self._afilt is not None:
-            self._fit_afilt(self._afilt)
-        for i, n, kind, B, A, tau, *agc in groups:
-            if kind is None:
-                raise ValueError("run_each needs an FM, MFM, WBFM, AM, USB or LSB demodulator on every channel")
-            ch = 2 if kind == hip.RCFM_WBFM else 1
-            audio = hip.empty((n, A, ch), self._torch.float32)
-            hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, 0, *agc), i, n,
-                                                  hip.ptr(audio), hip.stream()))
-            tones, mask = self._gates(handle, i, n, audio)
-            if masks is not None:
-                masks.append(mask)
-            if tone_out is not None:
-                tone_out.append(tones)
-            blocks.append((n, ch, audio))
-        self._open = masks
-        self._tone_out = tone_out
-        return blocks
+        if any(g[2] is None for g in groups):
+            raise ValueError("run_each needs an FM, MFM, WBFM, AM, USB or LSB demodulator on every channel")
+        return self._run_groups(handle, groups)
 
     def _each_result(self, blocks, device_output):
         out = []
@@ -988,8 +985,8 @@ class Tuner(Injector):
     def _batched_demod(self, kind, B, A, tau, chunk, agc=None):
         # one handle per geometry (and AGC setting), sized for all channels: rcfm_pipeline_run addresses the channels of
         # tuner and demodulator by the same index, so the per-channel state survives regrouping
-        opts = getattr(self, "_kernel_options", (True, True, True, 1, True))
-        key = (kind, len(self._bounds), B, A, tau, int(chunk)) + ((opts,) if opts != (True, True, True, 1, True) else ())
+        opts = self._kernel_options
+        key = (kind, len(self._bounds), B, A, tau, int(chunk)) + ((opts,) if opts != _DEFAULT_OPTIONS else ())
         if agc is not None:
             key += (("agc", agc),)
         if key not in self._batched:
@@ -1033,8 +1030,8 @@ class Tuner(Injector):
             self._state_owner[owner_key] = handle
         elif owner.value != handle.value:
             hip.check(self._lib.rcfm_demod_bind_state(handle.value, owner.value, 0, 0, hip.stream()))   # the owner has the history
-        if getattr(self, "_is_lane", False):
-            return                            # the channels' demodulator objects stay bound to the base tuner's handle
+        if self._is_lane:
+            return                          # the channels' demodulator objects stay bound to the base tuner's handle
         geo = (kind, B, A, tau) + ((agc,) if agc is not None else ())
         seen = set()
         for c in self._bounds:
@@ -1062,22 +1059,21 @@ class Tuner(Injector):
         t = Tuner(cuda=self._cuda)
         t._arena = self._arena
         t._is_lane = True
+        t._state_fence = True
+        t._state_owner = self._state_owner        # shared, the same dicts: one de-emphasis state per channel, whoever runs it ...
+        t._afilt_handles = self._afilt_handles    # ... and one audio filter state; every other device handle is the lane's own
         t._sync_lane(self)
         return t
 
     def _sync_lane(self, base):
-        if self._squelch is not base._squelch:             # the base's squelch setting (a new object per set_squelch)
-            self._squelch, self._squelch_dev, self._open = base._squelch, None, None
-        if self._tones is not base._tones:                 # ... its tone bank and tone squelch (a new object per set_tones)
-            self._tones, self._tones_dev, self._tone_out, self._open, self._tones_ready = base._tones, None, None, None, None
-        if self._afilt is not base._afilt:                 # ... its audio filter (a new object per set_audio_filter) and that filter's states
-            self._afilt, self._afilt_dev, self._afilt_ready = base._afilt, None, None
-        self._afilt_handles = base._afilt_handles
-        self._iq_balance = base._iq_balance                # ... its IQ balance (the next load applies it; per buffer, nothing to fence)
-        if self._blanker is not base._blanker:             # ... and its noise blanker, with a handle and scratch of this lane's own
-            self._blanker, self._blank_handles, self._blank_scratch = base._blanker, {}, None
-        if self._fine is not base._fine:                   # ... and its fine-tune (a new object per retune): the next load applies it
-            self._fine, self._abi_arrays = base._fine, None
+        """Follow the base tuner: its settings, each a new object per set_* -- what this lane made from the old one is made
+        again when it is next used (_derived), on the lane's own stream -- and its channel list."""
+        if self._tones is not base._tones or self._squelch is not base._squelch:
+            self._last = _Run()                            # (Lanes keeps each buffer's results with its ticket)
+        if self._blanker is not base._blanker:
+            self.set_blanker(None)                         # the handle and scratch of this lane's own go with their blanker
+        self._squelch, self._tones, self._afilt, self._iq_balance, self._blanker, self._fine = \
+            base._squelch, base._tones, base._afilt, base._iq_balance, base._blanker, base._fine
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
                 self._input_bandwidth == base._input_bandwidth:
             return
@@ -1086,9 +1082,6 @@ class Tuner(Injector):
         self._lo, self._hi, self._bw_sum = base._lo, base._hi, base._bw_sum
         self._version = base._version
         self._win_size = base._win_size
-        self._state_owner = base._state_owner          # one state per channel, whoever runs it
-        self._state_fence = True
-        if hasattr(base, "_kernel_options"):
-            self._kernel_options = base._kernel_options
+        self._kernel_options = base._kernel_options
         if base._shard is not None and self._shard != base._shard:
             self.shard(*base._shard)
