@@ -96,6 +96,7 @@ typedef struct rcfm_demod_s* rcfm_demod_t;
 typedef struct rcfm_subcarrier_s* rcfm_subcarrier_t;
 typedef struct rcfm_tone_bank_s* rcfm_tone_bank_t;
 typedef struct rcfm_audio_filter_s* rcfm_audio_filter_t;
+typedef struct rcfm_gate_s* rcfm_gate_t;
 typedef struct rcfm_resampler_s* rcfm_resampler_t;
 typedef struct rcfm_feeder_s* rcfm_feeder_t;
 typedef struct rcfm_comm_s* rcfm_comm_t;
@@ -597,6 +598,80 @@ int rcfm_audio_filter_get_state(rcfm_audio_filter_t f, double* state_host, void*
 int rcfm_audio_filter_set_state(rcfm_audio_filter_t f, const double* state_host, void* stream);
 int rcfm_audio_filter_set_fence(rcfm_audio_filter_t f, int on);
 int rcfm_audio_filter_destroy(rcfm_audio_filter_t f);
+
+/* ---- frame gate: time-resolved squelch with hysteresis, hang time and look-ahead (no reference counterpart) --------------
+ * rcfm_squelch decides once per buffer and keeps no memory.  The frame gate cuts the buffer into F frames, measures each
+ * frame's power, and walks a per-channel state machine over them that is carried from buffer to buffer: a transmission
+ * that starts inside a buffer opens from its first frame, a level near the threshold does not chatter, and a speaker's
+ * pause does not close the channel.
+ *
+ * rcfm_frame_power.  x is [rows][n], float32 (is_complex = 0) or complex64 (is_complex != 0); power is [rows][F] float32,
+ * F = floor(n / L): power[r][f] = (1 / L) sum_{i < L} |x[r][f L + i]|^2.  The tail n mod L is not read.  Squares and sums
+ * are float64 on the float32 values, the result is divided by L and rounded once to float32.  A frame is m = L or 2 L
+ * floats.  Up to 4096 floats it belongs to one wave (four frames to a workgroup, never a frame shared between waves); a
+ * longer one is cut into segments of 16384 floats, one workgroup each, whose float64 sums a second kernel adds in segment
+ * order (the partial sums live in a library-owned buffer per stream, grown by the first call that needs more).  Inside a
+ * wave or workgroup the floats are taken in groups of four, group g by lane g mod 64 (thread g mod 256), element e of every
+ * group into the lane's accumulator e, the lanes' sums in a fixed tree, the waves' sums in order.  No atomics; the order of
+ * every sum is a function of (L, is_complex) alone: bit-identical from run to run, between streams, for a sub-range of rows
+ * and whatever the rows' alignment -- the alignment of a frame's first float only picks the load, 16 bytes per lane, else
+ * 8, else 4.  RCFM_ERR_ARG before any device call: a NULL pointer, rows < 0, L < 1, L > n, L > 2^30, x not aligned for its
+ * element or power not for a float, rows F above 2^31 - 1.
+ *
+ * rcfm_tuner_frame_levels.  power [count][F] float32: the frame power of the samples rcfm_tuner_run returns for channels
+ * first .. first + count - 1, frames of B / F samples.  Readiness and the shared-bandwidth rule are rcfm_tuner_run's
+ * (RCFM_ERR_STATE, RCFM_ERR_INDEX, RCFM_ERR_ARG); F must divide B, else RCFM_ERR_ARG.  scratch is caller-owned device memory
+ * for m = floor(scratch_bytes / (8 B)) >= 1 channels.  The call IS, chunk by chunk on `stream`,
+ *   for (i = 0; i < count; i += m)  rcfm_tuner_run(t, first + i, min(m, count - i), scratch, stream);
+ *                                   rcfm_frame_power(scratch, min(m, count - i), B, 1, B / F, power + i F, stream);
+ * so it costs one more inverse pass of the channels plus 8 B bytes written and read per channel; the mean of a channel's
+ * frames is rcfm_tuner_levels' value up to the rounding of the inverse FFT.
+ *
+ * The gate.  State: (open, hang_left) per channel, int32 [C][2], addressed by channel index; zero after create and reset.
+ * create     hang: frames a channel stays open below close_thr; lead: frames of look-ahead; ramp_host [R] float32, the
+ *            rising edge's gains (Tuner builds 0.5 - 0.5 cos(pi (i + 1) / (R + 1)) in float64, rounded once), R >= 0.
+ *            RCFM_ERR_ARG before any device call: out NULL, C < 1, hang < 0, lead < 0, R outside 0 .. 2^20, R > 0 with
+ *            ramp_host NULL, a ramp element that is not finite.
+ * run        power [count][F], open_thr and close_thr [count] float32, frame_mask [count][F + 1] uint8, open_any [count]
+ *            uint8 or NULL, all on the device and all indexed by row: row i is channel first + i, whose state slot it uses.
+ *            One thread per channel walks the frames in order:
+ *              column 0 of frame_mask is the state's `open` on entry (the previous buffer's last frame, undilated);
+ *              for each frame with power p:  if p >= open_thr: open = 1, hang_left = hang;
+ *                                            else if open and p >= close_thr: hang_left = hang;
+ *                                            else if open: hang_left > 0 ? hang_left -= 1 : open = 0;
+ *              comparisons with NaN are false; g[f] = open.
+ *            Look-ahead: g'[f] = g[f] | g[f + 1] | ... | g[min(f + lead, F - 1)], so a transmission's onset is not clipped;
+ *            frame_mask[c][f + 1] = g'[f]; open_any[c] = g'[0] | ... | g'[F - 1] | column 0 (a channel that closes exactly at
+ *            the buffer edge still gets its ramp-down published).  The stored state is the undilated one.
+ *            RCFM_ERR_ARG before any device call: a NULL handle, power, threshold or frame_mask, count < 0, F outside
+ *            1 .. 65535, a pointer not aligned for a float.  RCFM_ERR_INDEX: first < 0 or first + count > C.
+ * apply      audio [count][A][ch] float32, ch in {1, 2}, in place; F must divide A, La = A / F.  Frame f of row c, with
+ *            g = frame_mask[c][f + 1] and gp = frame_mask[c][f], samples i < La, both legs alike:
+ *              g = 1, gp = 1   neither read nor written
+ *              g = 0, gp = 0   +0.0f stored
+ *              g = 1, gp = 0   x r[i] for i < R, untouched from R on
+ *              g = 0, gp = 1   x r[R - 1 - i] for i < R, +0.0f from R on
+ *            The multiply is one float32 product.  16-byte stores where La ch is a multiple of 4 and audio is 16-byte
+ *            aligned, else 4-byte stores.  It touches no state.  RCFM_ERR_ARG before any device call: a NULL handle, mask or
+ *            audio, count < 0, F outside 1 .. 65535, A < 1, F not dividing A, ch outside {1, 2}, audio not aligned for a
+ *            float, R > A / F.
+ * run and apply are asynchronous on `stream`, without a device allocation or a host synchronisation.
+ * reset      all states back to zero, on `stream`.
+ * get_state / set_state   the whole state, int32 [C][2], to / from the host; both wait for `stream`.
+ * set_fence  as rcfm_audio_filter_set_fence: when on, a run waits for the event the previous run of this handle recorded
+ *            and records its own.  Off by default, and then no event is touched. */
+int rcfm_frame_power(const void* x, int rows, int64_t n, int is_complex, int L, void* power, void* stream);
+int rcfm_tuner_frame_levels(rcfm_tuner_t t, int first, int count, int F, void* scratch, size_t scratch_bytes, void* power,
+                            void* stream);
+int rcfm_gate_create(int C, int hang, int lead, const float* ramp_host, int R, rcfm_gate_t* out);
+int rcfm_gate_run(rcfm_gate_t g, int first, int count, int F, const void* power, const void* open_thr, const void* close_thr,
+                  void* frame_mask, void* open_any, void* stream);
+int rcfm_gate_apply(rcfm_gate_t g, const void* frame_mask, int count, int F, int A, int ch, void* audio, void* stream);
+int rcfm_gate_reset(rcfm_gate_t g, void* stream);
+int rcfm_gate_get_state(rcfm_gate_t g, int32_t* state_host, void* stream);
+int rcfm_gate_set_state(rcfm_gate_t g, const int32_t* state_host, void* stream);
+int rcfm_gate_set_fence(rcfm_gate_t g, int on);
+int rcfm_gate_destroy(rcfm_gate_t g);
 
 /* ---- noise blanker: impulse noise removed from the wideband buffer, ahead of the FFT (no reference counterpart) -----------
  * A pulse of a few samples (ignition, switching supplies, electric fences) is white across the band: after rcfm_tuner_load it

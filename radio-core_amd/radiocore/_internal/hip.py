@@ -37,6 +37,7 @@ RCFM_IQ_BALANCE_OFF, RCFM_IQ_BALANCE_FIXED, RCFM_IQ_BALANCE_AUTO = 0, 1, 2   # r
 RCFM_IQ_SEG_PAIRS, RCFM_IQ_MAX_SEGS = 16384, 1024   # mirror pairs per workgroup of an estimate, and the most workgroups (csrc/iq_balance.h)
 RCFM_TONE_MAX_K, RCFM_TONE_SEGMENT = 64, 8192    # tones of a bank; samples of a frame per workgroup (csrc/tones.h)
 RCFM_SOS_MAX_SECTIONS, RCFM_SOS_RUN, RCFM_SOS_SEGMENT = 8, 33, 8192    # sections of an audio filter; samples per thread; floats per sweep (csrc/audio_filter.h)
+RCFM_GATE_WAVE_FLOATS, RCFM_GATE_SEG_FLOATS, RCFM_GATE_MAX_FRAMES, RCFM_GATE_MAX_RAMP = 4096, 16384, 65535, 1 << 20    # floats of a frame one wave takes; per workgroup of a longer one; F and R of a gate (csrc/gate.h)
 RCFM_TUNER_OPT_NARROW_TILES,RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                              # rcfm_tuner_set_option
 
 _ERR_SIZE, _ERR_INDEX, _ERR_RUNTIME, _ERR_ARG, _ERR_STATE = -1, -2, -3, -4, -5
@@ -128,6 +129,16 @@ SIGNATURES = {
     "rcfm_audio_filter_set_state": [_vp, ctypes.POINTER(_dbl), _vp],
     "rcfm_audio_filter_set_fence": [_vp, _i],
     "rcfm_audio_filter_destroy": [_vp],
+    "rcfm_frame_power": [_vp, _i, _i64, _i, _i, _vp, _vp],
+    "rcfm_tuner_frame_levels": [_vp, _i, _i, _i, _vp, _sz, _vp, _vp],
+    "rcfm_gate_create": [_i, _i, _i, _fp, _i, ctypes.POINTER(_vp)],
+    "rcfm_gate_run": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rcfm_gate_apply": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "rcfm_gate_reset": [_vp, _vp],
+    "rcfm_gate_get_state": [_vp, ctypes.POINTER(ctypes.c_int32), _vp],
+    "rcfm_gate_set_state": [_vp, ctypes.POINTER(ctypes.c_int32), _vp],
+    "rcfm_gate_set_fence": [_vp, _i],
+    "rcfm_gate_destroy": [_vp],
     "rcfm_blanker_create": [_i64, _i, _i, _i, _dbl, _i, _fp, _i, ctypes.POINTER(_vp)],
     "rcfm_blanker_run": [_vp, _i, _i64, _vp, _vp, _vp, _vp],
     "rcfm_blanker_destroy": [_vp],

@@ -100,11 +100,13 @@ class Lanes:
         _, end = self._spans[earlier]
         return float(start.elapsed_time(end))
 
-    def result(self, ticket: int, numpy_output: bool = True, open_mask: bool = False, tones: bool = False):
+    def result(self, ticket: int, numpy_output: bool = True, open_mask: bool = False, tones: bool = False,
+               frame_mask: bool = False):
         """The audio of one submitted buffer, [C, A, ch] float32 (the shard's block after Tuner.shard).
         open_mask=True: ``(audio, mask)`` with the squelch's numpy bool [C] of that buffer (Tuner.open_mask; None when
-        the buffer was submitted with squelch off).  tones=True: the tone bank's ``(P, E)`` of that buffer
-        (Tuner.tone_power; None when it was submitted without a bank) comes last in the tuple."""
+        the buffer was submitted with squelch off).  frame_mask=True: the frame gate's numpy bool [C, frames] of that
+        buffer follows (Tuner.frame_mask; None when it was submitted without a gate).  tones=True: the tone bank's
+        ``(P, E)`` of that buffer (Tuner.tone_power; None when it was submitted without a bank) comes last in the tuple."""
         entry = self._pending.pop(ticket)
         run = entry.run
         device_output = self._base._cuda and not numpy_output
@@ -120,6 +122,8 @@ class Lanes:
         extra = []
         if open_mask:
             extra.append(Tuner._mask_result(run.masks) if run.masks is not None else None)
+        if frame_mask:
+            extra.append(Tuner._frame_result(run.frames) if run.frames is not None else None)
         if tones:
             if device_output and run.tones is not None:
                 for p, e in run.tones:

@@ -10,7 +10,7 @@ buffer.  Host numpy only; under sharding every rank calls it on its own range an
 
 import numpy as np
 
-__all__ = ["threshold_over_floor"]
+__all__ = ["threshold_over_floor"]          # (segments: by its module, radiocore.tools.squelch.segments)
 
 
 def threshold_over_floor(levels, bandwidths, db):
@@ -24,3 +24,23 @@ def threshold_over_floor(levels, bandwidths, db):
         raise ValueError("bandwidths must be positive")
     density = float(np.median(levels / bandwidths))
     return (density * bandwidths * 10.0 ** (float(db) / 10.0)).astype(np.float32)
+
+
+def segments(frame_mask, A):
+    """What a publisher sends of a buffer gated by a ``FrameGate``: ``[(channel, start_sample, stop_sample)]``, the runs of
+    consecutive open frames of ``frame_mask`` (bool [C, F], ``Tuner.frame_mask()``) in audio samples of a row of ``A``
+    (half-open, channel by channel, ascending).  The fade-out of a channel that closes lies in the first closed frame; a
+    publisher that wants it sends ``min(stop_sample + ramp, A)``."""
+    m = np.asarray(frame_mask, dtype=bool)
+    if m.ndim != 2 or m.shape[1] < 1:
+        raise ValueError("frame_mask is [channels, frames]")
+    F = m.shape[1]
+    if int(A) < 1 or int(A) % F:
+        raise ValueError("%d frames do not divide a row of %d samples" % (F, int(A)))
+    La = int(A) // F
+    edges = np.diff(np.pad(m.astype(np.int8), ((0, 0), (1, 1))), axis=1)         # +1 where a run starts, -1 behind its end
+    out = []
+    for c in range(m.shape[0]):
+        starts, stops = np.flatnonzero(edges[c] == 1), np.flatnonzero(edges[c] == -1)
+        out.extend((c, int(a) * La, int(b) * La) for a, b in zip(starts, stops))
+    return out

@@ -23,8 +23,10 @@ _STATELESS = (hip.RCFM_FM, hip.RCFM_AM, hip.RCFM_USB, hip.RCFM_LSB)    # kinds w
                                                                        # (unless AM / USB / LSB carry an AGC: its state is bound and fenced)
 _DEFAULT_OPTIONS = (True, True, True, 1, True)                         # set_kernel_options: lds_chain, fused_tiles, phase_link, narrow_tiles, ssb_direct
 # What one run_all / run_each queued, on the device, one entry per launch group: blocks [(n, ch, audio [n, A, ch])]; masks, the
-# squelch's uint8 [n], or None (no squelch was set, or nothing was gated); tones, the bank's (P, E), or None (no bank was set).
-_Run = namedtuple("_Run", "blocks masks tones", defaults=(None, None, None))
+# squelch's uint8 [n], or None (no squelch was set, or nothing was gated); tones, the bank's (P, E), or None (no bank was set);
+# frames, the frame gate's uint8 [n, F + 1], or None (no gate was set).
+_Run = namedtuple("_Run", "blocks masks tones frames", defaults=(None, None, None, None))
+_FRAME_SCRATCH_BYTES = 256 << 20                                       # frame_levels: the most channel IQ held at a time
 
 
 def _key_agc(key):
@@ -90,12 +92,15 @@ class Tuner(Injector):
         self._tones = None         # set_tones: None (off) or (bank, want int32 [C] or None, ratio float32 [C] or None)
         self._afilt = None         # set_audio_filter: None (off) or (AudioFilter, uint8 [C] or None)
         self._blanker = None       # set_blanker: None (off) or (NoiseBlanker, in_place)
+        self._gate = None          # set_gate: None (off) or (FrameGate, open float32, close float32: 0-d or [len(channels())])
         # What is made FROM a setting -- device copies, "fits this launch plan", what the device handle was last told -- is
         # looked up with what it is made from (_derived) and made again when that differs: nothing invalidates it by hand.
         self._built = {}           # name -> (setting, channel-list version / launch-plan key / handle key, what was made)
         self._last = _Run()        # masks and tone powers of the last run_all / run_each (not its audio: the caller's)
         # Device state that is no copy of a setting: the filter's, shared by a lane, and the blanker's, each lane's own.
         self._afilt_handles = {}   # (legs, A) -> (channels, AudioFilter, librcfm handle): the filter's states, by channel index
+        self._gate_handles = {}    # A -> (channels, FrameGate, librcfm handle): the gate's states, by channel index, shared by a lane
+        self._frame_scratch = None # frame_levels: the channel IQ of a chunk, this device tuner's own (allocated by the first call, kept)
         self._blank_handles = {}   # buffer length n -> (the NoiseBlanker it was made by, librcfm handle): this device tuner's own scratch
         self._blank_scratch = None # the blanked copy of a caller's device tensor (buffer's dtype and size; allocated by the first such load)
         self._blank_counts = None  # device int64 [2] of the last load with a blanker: hits, samples with gain below 1
@@ -139,6 +144,7 @@ class Tuner(Injector):
         self._bounds = []
         self._lo = self._hi = self._bw_sum = None
         self._afilt_handles.clear()        # the audio filter's states belong to the channels
+        self._gate_handles.clear()         # ... and so do the frame gate's
         self._recalculate()
 
     def _recalculate(self, added=None):
@@ -598,7 +604,10 @@ class Tuner(Injector):
         decision is per buffer, on the device and on the caller's stream (no host synchronisation), and the
         demodulators still run on every channel: the de-emphasis state advances as without squelch.  A NaN threshold
         keeps a channel closed.  ``None`` (the default) turns squelch off: nothing more is launched than before.
-        ``squelch.threshold_over_floor`` derives thresholds from a ``levels()`` pass."""
+        ``squelch.threshold_over_floor`` derives thresholds from a ``levels()`` pass.  ValueError while a frame gate is set
+        (``set_gate``): the two take the same place."""
+        if threshold is not None and self._gate is not None:
+            raise ValueError("set_squelch: a frame gate is set (set_gate); turn it off first")
         self._squelch = None if threshold is None else self._per_channel(        # (np.array: a copy, a new object per setting)
             np.array(threshold, dtype=np.float32), "squelch thresholds: a scalar or one per channel")
         self._last = self._last._replace(masks=None)
@@ -772,19 +781,178 @@ class Tuner(Injector):
         hip.check(self._lib.rcfm_audio_filter_run(self._afilt_handle(ch, A), first, count, A, hip.ptr(audio), hip.ptr(audio),
                                                   sel, hip.stream()))
 
+    # ---- frame levels and the frame gate (rcfm_tuner_frame_levels / rcfm_gate_*; no reference counterpart) ---------------
+
+    def _bandwidth_runs(self):
+        """[(first, count, B)]: the runs of consecutive channels of one bandwidth in the launch plan's range, once per
+        (channel list, shard)."""
+        def make():
+            _, first, count = self._launch_plan()
+            runs, i = [], first
+            while i < first + count:
+                B, j = int(self._bounds[i].bandwidth), i + 1
+                while j < first + count and int(self._bounds[j].bandwidth) == B:
+                    j += 1
+                runs.append((i, j - i, B))
+                i = j
+            return runs
+        self._launch_plan()
+        return self._derived("bandwidth runs", None, self._plan[0], make)
+
+    def _frame_levels(self, handle, first, count, B, F, power_ptr):
+        # rcfm_tuner_frame_levels of one run of like channels on the current stream, through this device tuner's scratch
+        m = max(1, min(count, _FRAME_SCRATCH_BYTES // (8 * B)))
+        s = self._frame_scratch
+        if s is None or int(s.numel()) < m * B:
+            s = self._frame_scratch = hip.empty((m * B,), self._torch.complex64)
+        hip.check(self._lib.rcfm_tuner_frame_levels(handle, first, count, F, hip.ptr(s), ctypes.c_size_t(8 * int(s.numel())),
+                                                    power_ptr, hip.stream()))
+
+    def frame_levels(self, frames, numpy_output: bool = True):
+        """``levels()`` resolved in time: float32 [count, frames], the mean power of each of the ``frames`` equal frames of
+        every channel's samples of the loaded buffer (of the shard's range after ``shard``), in the units of ``levels()``;
+        the mean over a channel's frames is its level.  A read like ``levels()``: valid after ``load`` / ``adopt``, it needs
+        no gate and touches no state.  It runs the channels' inverse FFT once more, a chunk of channels at a time through a
+        scratch of at most 256 MB that the tuner keeps.  ValueError unless ``frames`` divides every channel's bandwidth."""
+        handle = self._ready()
+        F = int(frames)
+        if F != frames or F < 1:
+            raise ValueError("frames: a positive integer, not %r" % (frames,))
+        _, first, count = self._launch_plan()
+        runs = self._bandwidth_runs()
+        for _, _, B in runs:
+            if B % F:
+                raise ValueError("%d frames do not divide a channel of %d samples" % (F, B))
+        power = hip.empty((count, F), self._torch.float32)
+        for lo, n, B in runs:
+            self._frame_levels(handle, lo, n, B, F, ctypes.c_void_p(power.data_ptr() + 4 * F * (lo - first)))
+        return self._out(power, numpy_output)
+
+    def set_gate(self, gate=None, open=None, close=None, hysteresis_db: float = 3.0):
+        """A squelch that is right to a frame, not to a buffer: with a ``radiocore.FrameGate``, ``run_all`` / ``run_each`` /
+        ``run_all_packed`` (and ``Lanes.submit``) measure every frame of every channel (``frame_levels``), walk the gate's
+        state machine over them -- open at ``open``, held at ``close``, hang time, look-ahead -- and zero the closed frames
+        of the audio with a short fade at the edges, on the device and on the caller's stream, in the level squelch's place:
+        behind the tone bank and the audio filter, ahead of the tone squelch.  ``open_mask()`` tells which channels had
+        anything open in the buffer (``run_all_packed``, the ``Drain`` and ``wire.frames_packed`` work on it unchanged),
+        ``frame_mask()`` which frames.  ``open`` and ``close``: in the units of ``levels()``, a scalar or one per channel
+        (``squelch.threshold_over_floor`` gives ``open``); ``close`` defaults to ``open`` lowered by ``hysteresis_db``.  The
+        state is one per channel, carried from buffer to buffer, kept when channels are added, zeroed by ``reset_states()``
+        and dropped by ``reset()`` and by another gate.  ``None`` (the default) turns it off: nothing more is launched than
+        before.  ValueError -- the setting in force stays -- for ``close`` above ``open``, while ``set_squelch`` is set, and,
+        here or for channels added later in the next run before anything of it is launched, for frames that do not
+        divide a channel's bandwidth or audio length, or thresholds of another length."""
+        if gate is None:
+            if open is not None or close is not None:
+                raise ValueError("set_gate: thresholds need a gate")
+            self._gate = None
+            self._gate_handles.clear()
+        else:
+            if not hasattr(gate, "ramp_array") or not hasattr(gate, "_create"):
+                raise ValueError("set_gate takes a radiocore.FrameGate")
+            if self._squelch is not None:
+                raise ValueError("set_gate: a level squelch is set (set_squelch); turn it off first")
+            if open is None:
+                raise ValueError("set_gate: a gate needs its open threshold")
+            what = "gate thresholds: a scalar or one per channel"
+            o = self._per_channel(np.array(open, dtype=np.float32), what)
+            if close is None:
+                c = (o.astype(np.float64) * 10.0 ** (-float(hysteresis_db) / 10.0)).astype(np.float32)
+            else:
+                c = self._per_channel(np.array(close, dtype=np.float32), what)
+            if np.any(c > o):
+                raise ValueError("set_gate: close lies above open")
+            setting = (gate, o, c)
+            self._fit_gate(setting)                # refused here, with the old setting still in force
+            if self._gate is None or self._gate[0] is not gate:
+                self._gate_handles.clear()         # another gate: every channel starts closed
+            self._gate = setting
+        self._last = self._last._replace(masks=None, frames=None)
+
+    def _fit_gate(self, setting):
+        """The gate's frames against the bandwidth and audio length of every group of the launch plan, and the thresholds'
+        length: whatever is wrong raises here, before a run has advanced any state."""
+        if setting is None or not self._bounds:
+            return
+
+        def check():
+            gate, C = setting[0], len(self._bounds)
+            for a in setting[1:]:
+                if a.ndim == 1 and a.shape[0] != C:
+                    raise ValueError("gate thresholds were set for %d channels, the tuner has %d" % (a.shape[0], C))
+            for g in self._launch_plan()[0]:
+                if g[2] is not None:
+                    gate.fits(g[3])
+                    gate.ramp_samples(g[4])
+        self._launch_plan()
+        self._derived("gate fit", setting, self._plan[0], check)
+
+    def frame_mask(self):
+        """numpy bool [count, frames]: which frames of which channels the frame gate left open in this tuner's last
+        ``run_all`` / ``run_each`` -- look-ahead included, the tone squelch's verdict not (``open_mask()`` has that)."""
+        if self._last.frames is None:
+            raise RuntimeError("frame_mask: no run_all / run_each with a frame gate set (set_gate) yet")
+        return self._frame_result(self._last.frames)
+
+    @staticmethod
+    def _frame_result(frames):
+        return np.concatenate([hip.to_host(m)[:, 1:] for m in frames]).astype(bool)
+
+    def _gate_handle(self, A):
+        # one handle per audio rate (the fade's length follows it), sized for all channels: its state slots are addressed
+        # by channel index, so shard and regrouping keep them; a longer channel list takes the states over
+        C, gate = len(self._bounds), self._gate[0]
+        ent = self._gate_handles.get(A)
+        if ent is not None and ent[0] == C and ent[1] is gate:
+            return ent[2].value
+        h = gate._create(C, A)
+        if ent is not None and ent[1] is gate:
+            ip = ctypes.POINTER(ctypes.c_int32)
+            old = np.zeros((ent[0], 2), np.int32)
+            hip.check(self._lib.rcfm_gate_get_state(ent[2].value, old.ctypes.data_as(ip), hip.stream()))
+            new = np.zeros((C, 2), np.int32)
+            new[:min(C, ent[0])] = old[:min(C, ent[0])]
+            hip.check(self._lib.rcfm_gate_set_state(h.value, new.ctypes.data_as(ip), hip.stream()))
+        if self._state_fence:
+            hip.check(self._lib.rcfm_gate_set_fence(h.value, 1))
+        self._gate_handles[A] = (C, gate, h)
+        return h.value
+
+    def _gate_group(self, handle, first, count, audio):
+        # behind the group's audio filter on the same stream: frame levels of its channels, the state machine, then the
+        # zero fill and fades in place.  (open_any uint8 [count], frame mask uint8 [count, F + 1])
+        def upload():
+            C = len(self._bounds)
+            return tuple(hip.to_device(np.array(np.broadcast_to(a, (C,))), self._torch.float32) for a in self._gate[1:])    # (a copy: writable)
+        thr_open, thr_close = self._derived("gate thresholds", self._gate, self._version, upload)
+        F = self._gate[0].frames
+        A, ch = int(audio.shape[1]), int(audio.shape[2])
+        t = self._torch
+        power = hip.empty((count, F), t.float32)
+        fmask = hip.empty((count, F + 1), t.uint8)
+        mask = hip.empty((count,), t.uint8)
+        g, s = self._gate_handle(A), hip.stream()
+        self._frame_levels(handle, first, count, int(self._bounds[first].bandwidth), F, hip.ptr(power))
+        hip.check(self._lib.rcfm_gate_run(g, first, count, F, hip.ptr(power), ctypes.c_void_p(thr_open.data_ptr() + 4 * first),
+                                          ctypes.c_void_p(thr_close.data_ptr() + 4 * first), hip.ptr(fmask), hip.ptr(mask), s))
+        hip.check(self._lib.rcfm_gate_apply(g, hip.ptr(fmask), count, F, A, ch, hip.ptr(audio), s))
+        return mask, fmask
+
     def _gates(self, handle, first, count, audio):
-        """What follows a group's rcfm_pipeline_run on the same stream: the tone bank, the audio filter, the level squelch,
-        the tone squelch, each only when set.  (tones (P, E) or None, open mask or None)."""
-        tones = mask = None
+        """What follows a group's rcfm_pipeline_run on the same stream: the tone bank, the audio filter, the level squelch
+        or the frame gate, the tone squelch, each only when set.  (tones (P, E) or None, open mask or None, frame mask or None)."""
+        tones = mask = frames = None
         if self._tones is not None:
             tones = self._tones[0].run(audio, step=int(audio.shape[2]), offset=0)
         if self._afilt is not None:
             self._filter_group(first, count, audio)
         if self._squelch is not None:
             mask = self._squelch_group(handle, first, count, audio)
+        elif self._gate is not None:
+            mask, frames = self._gate_group(handle, first, count, audio)
         if tones is not None and self._tones[1] is not None:
             mask = self._tone_squelch(first, count, audio, tones, mask)
-        return tones, mask
+        return tones, mask, frames
 
     def _squelch_group(self, handle, first, count, audio):
         # behind the group's rcfm_pipeline_run on the same stream: levels of its channels, then mask + zero fill
@@ -856,8 +1024,9 @@ class Tuner(Injector):
         before the first launch.  Returns the _Run and keeps its masks and tone powers for open_mask() / tone_power()."""
         self._fit_tones(self._tones)
         self._fit_afilt(self._afilt)
-        gated = self._squelch is not None or (self._tones is not None and self._tones[1] is not None)
-        run = _Run([], [] if gated else None, [] if self._tones is not None else None)
+        self._fit_gate(self._gate)
+        gated = self._squelch is not None or self._gate is not None or (self._tones is not None and self._tones[1] is not None)
+        run = _Run([], [] if gated else None, [] if self._tones is not None else None, [] if self._gate is not None else None)
         for first, count, kind, B, A, tau, *agc in groups:
             ch = 2 if kind == hip.RCFM_WBFM else 1
             audio = hip.empty((count, A, ch), self._torch.float32)
@@ -865,14 +1034,16 @@ class Tuner(Injector):
                                                   hip.ptr(audio), hip.stream()))
             run.blocks.append((count, ch, audio))
             if not count:                  # run_all of an empty shard: nothing to gate, and nothing to ask for afterwards
-                run = run._replace(masks=None, tones=None)
+                run = run._replace(masks=None, tones=None, frames=None)
                 continue
-            tones, mask = self._gates(handle, first, count, audio)
+            tones, mask, frames = self._gates(handle, first, count, audio)
             if run.masks is not None:
                 run.masks.append(mask)
             if run.tones is not None:
                 run.tones.append(tones)
-        self._last = _Run(None, run.masks, run.tones)
+            if run.frames is not None:
+                run.frames.append(frames)
+        self._last = _Run(None, run.masks, run.tones, run.frames)
         return run
 
     def run_all_packed(self, pcm, numpy_output: bool = True, chunk: int = 0, drain=None):
@@ -966,11 +1137,14 @@ class Tuner(Injector):
     def reset_states(self):
         """Every channel's de-emphasis state back to the reference's freshly constructed filters (deemphasis.py:48-49),
         and every AGC back to "no history": the batched handles of run_all / run_each, whose slots the channels'
-        demodulator objects share.  The audio filter's states (set_audio_filter) go back to rest as well."""
+        demodulator objects share.  The audio filter's states (set_audio_filter) go back to rest as well, and the frame
+        gate (set_gate) closes every channel."""
         for h in self._batched.values():
             hip.check(self._lib.rcfm_demod_reset_state(h.value, hip.stream()))
         for _, _, h in self._afilt_handles.values():
             hip.check(self._lib.rcfm_audio_filter_reset(h.value, hip.stream()))
+        for _, _, h in self._gate_handles.values():
+            hip.check(self._lib.rcfm_gate_reset(h.value, hip.stream()))
 
     def set_kernel_options(self, lds_chain=True, fused_tiles=True, phase_link=True, narrow_tiles=1, ssb_direct=True):
         """Which forms of the kernel chain run_all / run_each may use (rcfm_demod_set_option; no reference
@@ -1052,6 +1226,8 @@ class Tuner(Injector):
                 hip.check(self._lib.rcfm_demod_set_option(h.value, hip.RCFM_OPT_STATE_FENCE, 1))
         for _, _, h in self._afilt_handles.values():
             hip.check(self._lib.rcfm_audio_filter_set_fence(h.value, 1))
+        for _, _, h in self._gate_handles.values():
+            hip.check(self._lib.rcfm_gate_set_fence(h.value, 1))
 
     def _lane_clone(self):
         """A second Tuner over the SAME channel list, demodulator objects and de-emphasis state, with its own device
@@ -1061,19 +1237,20 @@ class Tuner(Injector):
         t._is_lane = True
         t._state_fence = True
         t._state_owner = self._state_owner        # shared, the same dicts: one de-emphasis state per channel, whoever runs it ...
-        t._afilt_handles = self._afilt_handles    # ... and one audio filter state; every other device handle is the lane's own
+        t._afilt_handles = self._afilt_handles    # ... and one audio filter state ...
+        t._gate_handles = self._gate_handles      # ... and one frame gate state; every other device handle is the lane's own
         t._sync_lane(self)
         return t
 
     def _sync_lane(self, base):
         """Follow the base tuner: its settings, each a new object per set_* -- what this lane made from the old one is made
         again when it is next used (_derived), on the lane's own stream -- and its channel list."""
-        if self._tones is not base._tones or self._squelch is not base._squelch:
+        if self._tones is not base._tones or self._squelch is not base._squelch or self._gate is not base._gate:
             self._last = _Run()                            # (Lanes keeps each buffer's results with its ticket)
         if self._blanker is not base._blanker:
             self.set_blanker(None)                         # the handle and scratch of this lane's own go with their blanker
-        self._squelch, self._tones, self._afilt, self._iq_balance, self._blanker, self._fine = \
-            base._squelch, base._tones, base._afilt, base._iq_balance, base._blanker, base._fine
+        self._squelch, self._tones, self._afilt, self._iq_balance, self._blanker, self._fine, self._gate = \
+            base._squelch, base._tones, base._afilt, base._iq_balance, base._blanker, base._fine, base._gate
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
                 self._input_bandwidth == base._input_bandwidth:
             return
