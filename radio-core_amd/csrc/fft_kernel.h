@@ -1092,6 +1092,28 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2(Ff
 
 // ---- one inverse transform in, two forward transforms out ------------------------------
 //
+// RCFM_PAIR_FORM (make EXTRA=-DRCFM_PAIR_FORM=n, for A/B builds from one tree): the form of k_fft_tile2_pair.
+//   0  as before this switch existed: early fetch at every length, 480 / 500 points in three LDS stages
+//   1  late fetch at the lengths pair_late_fetch names, 480 / 500 points still in three stages
+//   2  late fetch and 480 / 500 points in two stages of composite radices (RCFM_FFT_PAIR_LONG)
+// Same-address A/B of whole steps against form 0 (profiles/pair_two_stage_ab.txt; every repetition of form 2 below every
+// repetition of form 0): cfg4 (pair <480>) -0.9 / -1.2 / -0.9 %, B = 200 000 (<400>) -1.8 %, 250 000 (<500>) -3.1 %,
+// 256 000 (<512>) -3.3 %; form 1 is bit-identical to form 0 and measures the same at 480 (+0.1 %, sets overlap).  The
+// 480-point kernel: 1002 -> 901 us per launch (profiles/pair_two_stage_kernel_rates.md).
+#ifndef RCFM_PAIR_FORM
+#define RCFM_PAIR_FORM 2
+#endif
+// With the late fetch: member 1's own inputs are issued behind member 0's first stage (1) or in front of it (0).  Behind
+// it the two-stage forms hold no scratch (in front: 28 / 36 bytes per lane at 480 / 500, and cfg4 -0.7 % instead of -1.2 %).
+#ifndef RCFM_PAIR_M1_AFTER
+#define RCFM_PAIR_M1_AFTER 1
+#endif
+// Which lengths fetch member 0's own inputs late (MidOp contract below): the per-length choice, by scratch bytes per lane
+// in both tile widths (profiles/pair_two_stage_resources.md).  Today every length: none needs more scratch than with the
+// early fetch, 400 points lose their 60 bytes, 512 (8 x 8 x 8) go from 204 to 176 -- with member 1's fetch in front of
+// member 0's transform (RCFM_PAIR_M1_AFTER=0) that tile needed more than before and would have kept the early fetch.
+constexpr bool pair_late_fetch(int /*L*/) { return RCFM_PAIR_FORM != 0; }
+//
 // k_fft_tile2 for PAIRS of real signals that travelled through one complex transform: the first
 // transform's line belongs to pair P = blockIdx.z; the point-wise stage turns each of its values w
 // into one value per member (channels 2P and 2P+1), and each member gets its own second transform
@@ -1099,10 +1121,15 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2(Ff
 // analytic signals of two pilots come out of ONE masked inverse FFT (fused_passes.h).
 //
 // MidOp contract (natural-order point `off` of the tile, channel bases b0 / b1 in signal samples):
-//   In0 fetch0(b0, b1, off)          inputs needed for member 0 and for the split (issued early)
-//   float fetch1(b1, off)            what member 1 still needs (issued while member 0 transforms)
-//   float2 first(w, In0, Keep&)      member 0's value; Keep = what member 1 needs later
-//   float2 second(Keep, float)       member 1's value
+//   In0 fetch0(b0, b1, off)              what the split of w needs (issued before transform 1's last stage)
+//   float fetch1(b, off)                 a member's own point-wise input
+//   void first(w, In0, Keep&, Keep&)     the split: what each member carries to its point-wise stage
+//   float2 second(Keep, float)           a member's value from what it carried and its own input
+// Late fetch (pair_late_fetch(L)): member 0's own inputs are issued once transform 1's last stage has consumed the tile,
+// in front of the "every slot has been read" barrier, and member 1's while member 0 transforms: the split then runs
+// next to fetch0's loads only, and a thread carries two Keep per point instead of a finished float2 and one Keep.
+// Early fetch (the form before; RCFM_PAIR_FORM=0, or a length that pair_late_fetch excludes): member 0's inputs travel
+// with fetch0's and second() runs inside the last-stage loop.  Same arithmetic, same order, bit-identical results.
 template <int L, int R0, int R1, int R2, int R3, int T, class LoadOp, class MidOp, class StoreOp>
 __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pair(FftPassDev d1, FftPassDev d2, LoadOp load,
                                                                           MidOp mid, StoreOp store, int count) {
@@ -1182,43 +1209,91 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
         lds_barrier();
     }
 
-    // ---- point-wise inputs of member 0 (and of the split), then the last stage ----------------
+    // ---- point-wise inputs of the split (early fetch: and of member 0), then the last stage ------
+    constexpr bool LATE = pair_late_fetch(L);
     using In0 = decltype(mid.fetch0(mid_base0, mid_base1, 0u));
-    In0 a0[nitL * RL];
-#pragma unroll
-    for (int it = 0; it < nitL; ++it)
-#pragma unroll
-        for (int q = 0; q < RL; ++q)
-            a0[it * RL + q] = mid.fetch0(mid_base0 + q_off(q), mid_base1 + q_off(q), lane_off(it));
-
-    // Last stage of the first transform and the split, one butterfly row at a time (the inputs a0
-    // retire as the values u0 / keep appear: fewer registers than holding all of w first).
-    id.i = i0 + w;
     using Keep = typename MidOp::Keep;
-    float2 u0[nitL * RL];
+    In0 a0[nitL * RL];
+    float m0[nitL * RL];
     Keep keep[nitL * RL];
+    id.i = i0 + w;
+    if constexpr (LATE) {
 #pragma unroll
-    for (int it = 0; it < nitL; ++it) {
-        const int g = rg + RG * it;
-        if ((rowsL % RG == 0) || g < rowsL) {
-            float2 x[RL];
-#pragma unroll
-            for (int q = 0; q < RL; ++q) x[q] = tile[lds_slot<true>(g * RL + q, w)];
-            dft_p<RL>(x);
+        for (int it = 0; it < nitL; ++it)
 #pragma unroll
             for (int q = 0; q < RL; ++q)
-                u0[it * RL + q] = mid.first(x[dft_slot<RL>(q)], a0[it * RL + q], keep[it * RL + q]);
+                a0[it * RL + q] = mid.fetch0(mid_base0 + q_off(q), mid_base1 + q_off(q), lane_off(it));
+
+        // Last stage of the first transform and the split, one butterfly row at a time (the inputs a0
+        // retire as the carriers appear: fewer registers than holding all of w first).
+        Keep keep0[nitL * RL];
+#pragma unroll
+        for (int it = 0; it < nitL; ++it) {
+            const int g = rg + RG * it;
+            if ((rowsL % RG == 0) || g < rowsL) {
+                float2 x[RL];
+#pragma unroll
+                for (int q = 0; q < RL; ++q) x[q] = tile[lds_slot<true>(g * RL + q, w)];
+                dft_p<RL>(x);
+#pragma unroll
+                for (int q = 0; q < RL; ++q)
+                    mid.first(x[dft_slot<RL>(q)], a0[it * RL + q], keep0[it * RL + q], keep[it * RL + q]);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one row at a time: hoisted LDS reads of the next rows would spill
         }
-        __builtin_amdgcn_sched_barrier(0);   // one row at a time: hoisted LDS reads of the next rows would spill
-    }
-    lds_barrier();   // every slot has been read
+        // member 0's own inputs: issued back to back now that the tile's registers are free; they fly across the barrier
 #pragma unroll
-    for (int it = 0; it < nitL; ++it) {
-        const int g = rg + RG * it;
-        if ((rowsL % RG == 0) || g < rowsL) {
-            const int kb = last_stage_base<L, R0, R1, RL, S>(g);
+        for (int it = 0; it < nitL; ++it)
 #pragma unroll
-            for (int q = 0; q < RL; ++q) tile[lds_slot<true>(kb + (L / RL) * q, w)] = u0[it * RL + q];
+            for (int q = 0; q < RL; ++q) m0[it * RL + q] = mid.fetch1(mid_base0 + q_off(q), lane_off(it));
+        lds_barrier();   // every slot has been read
+#pragma unroll
+        for (int it = 0; it < nitL; ++it) {
+            const int g = rg + RG * it;
+            if ((rowsL % RG == 0) || g < rowsL) {
+                const int kb = last_stage_base<L, R0, R1, RL, S>(g);
+#pragma unroll
+                for (int q = 0; q < RL; ++q)
+                    tile[lds_slot<true>(kb + (L / RL) * q, w)] = mid.second(keep0[it * RL + q], m0[it * RL + q]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int it = 0; it < nitL; ++it)
+#pragma unroll
+            for (int q = 0; q < RL; ++q) {
+                a0[it * RL + q] = mid.fetch0(mid_base0 + q_off(q), mid_base1 + q_off(q), lane_off(it));
+                m0[it * RL + q] = mid.fetch1(mid_base0 + q_off(q), lane_off(it));
+            }
+
+        // As above, with member 0's value finished inside the loop (a0 and m0 retire as u0 / keep appear).
+        float2 u0[nitL * RL];
+#pragma unroll
+        for (int it = 0; it < nitL; ++it) {
+            const int g = rg + RG * it;
+            if ((rowsL % RG == 0) || g < rowsL) {
+                float2 x[RL];
+#pragma unroll
+                for (int q = 0; q < RL; ++q) x[q] = tile[lds_slot<true>(g * RL + q, w)];
+                dft_p<RL>(x);
+#pragma unroll
+                for (int q = 0; q < RL; ++q) {
+                    Keep k0;
+                    mid.first(x[dft_slot<RL>(q)], a0[it * RL + q], k0, keep[it * RL + q]);
+                    u0[it * RL + q] = mid.second(k0, m0[it * RL + q]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one row at a time: hoisted LDS reads of the next rows would spill
+        }
+        lds_barrier();   // every slot has been read
+#pragma unroll
+        for (int it = 0; it < nitL; ++it) {
+            const int g = rg + RG * it;
+            if ((rowsL % RG == 0) || g < rowsL) {
+                const int kb = last_stage_base<L, R0, R1, RL, S>(g);
+#pragma unroll
+                for (int q = 0; q < RL; ++q) tile[lds_slot<true>(kb + (L / RL) * q, w)] = u0[it * RL + q];
+            }
         }
     }
     lds_barrier();
@@ -1227,8 +1302,9 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
     const unsigned f = (unsigned)((int64_t)(i0 + w) * p2.tw_i);
     const float2 D = big_twiddle(d2, f * (unsigned)(L / RL));
     const bool lane_ok = w < wvalid;
-    auto second_transform = [&](int64_t out_base) {
+    auto second_transform = [&](int64_t out_base, auto&& after_first_stage) {
         stage_lds<L, R0, L, true, RG>(tile, tw, w, rg);
+        after_first_stage();
         lds_barrier();
         if constexpr (S >= 3) {
             stage_lds<L, R1, L / R0, true, RG>(tile, tw, w, rg);
@@ -1261,13 +1337,22 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
         }
     };
 
+    // Member 1's own inputs fly while member 0 transforms.  M1_AFTER: behind member 0's first stage, so that the widest
+    // butterfly of the kernel does not run next to them (they still have the rest of the transform to arrive).
+    constexpr bool M1_AFTER = LATE && RCFM_PAIR_M1_AFTER;
     float a1[nitL * RL];
+    auto fetch_a1 = [&]() {
 #pragma unroll
-    for (int it = 0; it < nitL; ++it)
+        for (int it = 0; it < nitL; ++it)
 #pragma unroll
-        for (int q = 0; q < RL; ++q) a1[it * RL + q] = mid.fetch1(mid_base1 + q_off(q), lane_off(it));
-
-    second_transform(out_base0);
+            for (int q = 0; q < RL; ++q) a1[it * RL + q] = mid.fetch1(mid_base1 + q_off(q), lane_off(it));
+    };
+    if constexpr (M1_AFTER) {
+        second_transform(out_base0, fetch_a1);
+    } else {
+        fetch_a1();
+        second_transform(out_base0, [] {});
+    }
     if (!has1) return;   // workgroup-uniform
     lds_barrier();     // member 0's last stage has read every slot
 #pragma unroll
@@ -1283,7 +1368,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_pa
         }
     }
     lds_barrier();
-    second_transform(out_base1);
+    second_transform(out_base1, [] {});
 }
 
 // ---- a long forward transform's last pass feeding a short inverse transform's first pass --------
@@ -1641,7 +1726,8 @@ namespace fftk {
 
 // Lengths with a compile-time specialisation (radices listed first stage first; they must
 // match choose_radices() in fft_engine.hip).  Other lengths run the generic kernel.
-// The 480- and 500-point tiles run two LDS stages of composite radices (dft_nat); the pair kernel keeps three.
+// The 480- and 500-point tiles run two LDS stages of composite radices (dft_nat); TABLE3 is the three-stage form the
+// pair kernel ran before its late fetch (RCFM_PAIR_FORM, k_fft_tile2_pair).
 #define RCFM_FFT_LONG_TABLE3(X) X(480, 10, 8, 6, 1) X(500, 10, 10, 5, 1)
 #define RCFM_FFT_LONG_TABLE(X) X(480, 24, 20, 1, 1) X(500, 25, 20, 1, 1)
 // Big tiles (fft_engine.h, kFftBigL): one 1024-thread workgroup per CU.  Two stages of radix 24..32 leave
@@ -1679,8 +1765,15 @@ namespace fftk {
     X(512, 8, 8, 8, 1)
 #define RCFM_FFT_FAST_LENGTHS(X) RCFM_FFT_LENGTHS_(X, RCFM_FFT_LONG_TABLE)
 // k_fft_tile2_pair keeps RL points per last-stage butterfly row in registers next to the point-wise
-// stage's inputs: with a last radix of 20 it spills, so it stays on three stages.
-#define RCFM_FFT_PAIR_LENGTHS(X) RCFM_FFT_LENGTHS_(X, RCFM_FFT_LONG_TABLE3)
+// stage's inputs, so its radix lists are a table of its own.  With member 0's mono samples fetched late
+// (pair_late_fetch) a last radix of 20 fits; with the early fetch it spilled 68 bytes per lane and the
+// kernel stayed on three stages (RCFM_PAIR_FORM 0 and 1 build that).
+#if RCFM_PAIR_FORM >= 2
+#define RCFM_FFT_PAIR_LONG RCFM_FFT_LONG_TABLE
+#else
+#define RCFM_FFT_PAIR_LONG RCFM_FFT_LONG_TABLE3
+#endif
+#define RCFM_FFT_PAIR_LENGTHS(X) RCFM_FFT_LENGTHS_(X, RCFM_FFT_PAIR_LONG)
 
 
 // Threads per tile.  Long tiles are LDS-limited to two workgroups per CU; 512 threads keep 16 waves per CU in flight

@@ -367,26 +367,25 @@ struct MidStereoMixPair {
     // takes its row pitch (16) and tile base from here instead of the plan
     int64_t stride = 0;
     int blk16 = 0;
-    struct In0 { float p0, p1, m0; };
-    using Keep = float;   // member 1's carrier s2 = Im(z1^2)/|z1^2|
+    struct In0 { float p0, p1; };
+    using Keep = float;   // a member's carrier s2 = Im(z^2)/|z^2|
     // uniform 64-bit base + 32-bit lane byte offset: one VGPR of address per point, shared by the
-    // three streams (54 loads per thread are in flight together)
+    // streams (the pilots' 2 x 20 loads per thread of a 480-point tile are in flight together, then the 20 of a mono signal)
     static __device__ __forceinline__ float at(const float* base, unsigned off) {
         return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)(off * 4u));
     }
     __device__ __forceinline__ In0 fetch0(int64_t b0, int64_t b1, unsigned off) const {
-        return In0{at(p + b0, off), at(p + b1, off), at(m + b0, off)};
+        return In0{at(p + b0, off), at(p + b1, off)};
     }
-    __device__ __forceinline__ float fetch1(int64_t b1, unsigned off) const { return at(m + b1, off); }
-    // v = w with re/im exchanged (inverse transform by the swap identity)
-    __device__ __forceinline__ float2 first(float2 v, const In0& a, Keep& s2_1) const {
+    __device__ __forceinline__ float fetch1(int64_t b, unsigned off) const { return at(m + b, off); }
+    // v = w with re/im exchanged (inverse transform by the swap identity); the mono samples are not needed for the split
+    __device__ __forceinline__ void first(float2 v, const In0& a, Keep& s2_0, Keep& s2_1) const {
         s2_1 = pilot_carrier(a.p1, a.p0 - v.y);
-        const float lmr = (pilot_carrier(a.p0, v.x - a.p1) * a.m0) * 1.0175f;
-        return make_float2(a.m0 + lmr, a.m0 - lmr);
+        s2_0 = pilot_carrier(a.p0, v.x - a.p1);
     }
-    __device__ __forceinline__ float2 second(const Keep& s2_1, float m1) const {
-        const float lmr = (s2_1 * m1) * 1.0175f;
-        return make_float2(m1 + lmr, m1 - lmr);
+    __device__ __forceinline__ float2 second(const Keep& s2, float mm) const {
+        const float lmr = (s2 * mm) * 1.0175f;
+        return make_float2(mm + lmr, mm - lmr);
     }
 };
 
