@@ -58,7 +58,8 @@ extern "C" {
                             rcfm_audio_filter_* added (new symbols only, nothing existing changed);
                             rcfm_subcarrier_describe added to rcfm_tools.h (a new host-only symbol, nothing existing changed);
                             rcfm_blanker_* added, rcfm_blanker_last in rcfm_tools.h, RCFM_IQ_CF32 = 0 named (new symbols only,
-                            nothing existing changed: the load entry points refuse format 0 as before) */
+                            nothing existing changed: the load entry points refuse format 0 as before);
+                            rcfm_rank_filter and rcfm_floor_* added (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -97,6 +98,7 @@ typedef struct rcfm_subcarrier_s* rcfm_subcarrier_t;
 typedef struct rcfm_tone_bank_s* rcfm_tone_bank_t;
 typedef struct rcfm_audio_filter_s* rcfm_audio_filter_t;
 typedef struct rcfm_gate_s* rcfm_gate_t;
+typedef struct rcfm_floor_s* rcfm_floor_t;
 typedef struct rcfm_resampler_s* rcfm_resampler_t;
 typedef struct rcfm_feeder_s* rcfm_feeder_t;
 typedef struct rcfm_comm_s* rcfm_comm_t;
@@ -672,6 +674,56 @@ int rcfm_gate_get_state(rcfm_gate_t g, int32_t* state_host, void* stream);
 int rcfm_gate_set_state(rcfm_gate_t g, const int32_t* state_host, void* stream);
 int rcfm_gate_set_fence(rcfm_gate_t g, int on);
 int rcfm_gate_destroy(rcfm_gate_t g);
+
+/* ---- noise floor: OS-CFAR thresholds from the power spectrum, tracked across buffers (no reference counterpart) -----------
+ * rcfm_squelch and the frame gate compare against absolute levels a host has to supply, and a band is not flat.  The noise
+ * floor takes, around every cell of rcfm_tuner_power_spectrum's output, an order statistic of the neighbouring cells (guard
+ * cells next to it left out, so a station does not raise its own floor), smooths it from buffer to buffer on the device and
+ * turns it into per-channel thresholds on the device: "10 dB over the floor here and now", without a host round trip.
+ *
+ * Ordering.  Values are ordered by value; -0 sorts below +0; every NaN sorts above +inf, and all NaNs are equal.  A NaN
+ * result is stored as 0x7fc00000.
+ *
+ * rcfm_rank_filter.  x, out: [M] float32 on the device, stateless.  The candidates of cell m are the cells j with
+ * 0 <= j < M and guard < |j - m| <= half: no padding, no reflection, at the band ends the window is shorter.  With cnt
+ * candidates, out[m] is the candidate of rank r = (q (cnt - 1)) / 1000 (64-bit integer division; 0-based, ascending in the
+ * ordering above), the bits of that input cell.  q = 0 is the minimum, 500 the (lower) median, 1000 the maximum.  A cell
+ * that has no candidate (possible for M < 2 guard + 2) gets NaN.  The selection is exact (a bisection over the 32 bits of
+ * an order-preserving key, counting the candidates below the pivot), so the output bits do not depend on how it is computed:
+ * the same from run to run, from stream to stream and for any alignment.  RCFM_ERR_ARG before any device call: a NULL
+ * pointer, out == x, M < guard + 2, M > 2^30, half outside 1 .. 4096, guard outside 0 .. half - 1, q outside 0 .. 1000, a
+ * pointer not aligned for a float.
+ *
+ * The handle.  State s [M] float32 on the device, all NaN ("not primed") after create and reset.
+ * create     M, half, guard, q as above; rise, fall: the smoothing factors, finite and in (0, 1].  RCFM_ERR_ARG before any
+ *            device call: out NULL, the refusals of rcfm_rank_filter, rise or fall outside (0, 1] or not finite.
+ * run        power [M] float32 device (rcfm_tuner_power_spectrum's); e = rank_filter(power); then per cell
+ *              s' = e                                     if s is NaN
+ *              s' = s                                     if e is NaN
+ *              s' = s + a (e - s), a = e > s ? rise : fall  else, as __fadd_rn(s, __fmul_rn(a, __fsub_rn(e, s))): three
+ *                                                          float32 roundings, no contraction
+ *            s' replaces s; floor [M] float32 = s'; over [M] uint8 = power[m] >= __fmul_rn(ratio, s'[m]) (false on NaN).
+ *            floor or over may be NULL, not both.  One kernel, asynchronous on `stream`, no device allocation, no host
+ *            synchronisation.  RCFM_ERR_ARG before any device call: a NULL handle or power, floor and over both NULL,
+ *            floor == power, a NaN ratio, power or floor not aligned for a float.
+ * reset      every state back to NaN, on `stream`.
+ * get_state / set_state   the whole state, float32 [M], to / from the host; both wait for `stream`.
+ * set_fence  as rcfm_gate_set_fence: when on, a run waits for the event the previous run of this handle recorded and
+ *            records its own.  Off by default, and then no event is touched.
+ *
+ * rcfm_floor_thresholds.  Stateless: thr[i] = __fmul_rn(floor[cell[i]], gain[i]), i < count; floor [M] float32, cell
+ * [count] int32, gain and thr [count] float32, all on the device.  A cell index outside [0, M) gives a NaN threshold --
+ * rcfm_squelch and rcfm_gate_run keep such a channel closed -- and nothing is read out of bounds.  RCFM_ERR_ARG before any
+ * device call: a NULL pointer, M outside 1 .. 2^30, count < 0, a pointer not aligned for four bytes. */
+int rcfm_rank_filter(const void* x, int64_t M, int half, int guard, int q, void* out, void* stream);
+int rcfm_floor_create(int64_t M, int half, int guard, int q, float rise, float fall, rcfm_floor_t* out);
+int rcfm_floor_run(rcfm_floor_t h, const void* power, float ratio, void* floor, void* over, void* stream);
+int rcfm_floor_thresholds(const void* floor, int64_t M, const void* cell, const void* gain, int count, void* thr, void* stream);
+int rcfm_floor_reset(rcfm_floor_t h, void* stream);
+int rcfm_floor_get_state(rcfm_floor_t h, float* state_host, void* stream);
+int rcfm_floor_set_state(rcfm_floor_t h, const float* state_host, void* stream);
+int rcfm_floor_set_fence(rcfm_floor_t h, int on);
+int rcfm_floor_destroy(rcfm_floor_t h);
 
 /* ---- noise blanker: impulse noise removed from the wideband buffer, ahead of the FFT (no reference counterpart) -----------
  * A pulse of a few samples (ignition, switching supplies, electric fences) is white across the band: after rcfm_tuner_load it

@@ -43,12 +43,14 @@ def cell_frequencies(input_frequency, s0, L, cells):
     return float(input_frequency) + int(s0) + 0.5 * (e[:-1] + e[1:] - 1)
 
 
-def occupied(power, db, min_cells=1, lengths=None):
+def occupied(power, db, min_cells=1, lengths=None, floor=None):
     """The occupied runs of a binned power spectrum: [(first_cell, last_cell, strongest_cell)], inclusive.
 
     The floor is the median power density, median(power / lengths) (lengths: bins per cell, one per cell or a scalar;
     None: equal cells); a cell is kept when its density is at least ``db`` dB above it, and every contiguous run of at
-    least ``min_cells`` kept cells is reported with the cell of its highest power."""
+    least ``min_cells`` kept cells is reported with the cell of its highest power.  ``floor``: one value per cell in the
+    units of ``power`` (``Tuner.floor()``) takes the global median's place -- a cell is kept when its power is at least
+    ``db`` dB above its own floor; a cell whose floor is NaN is not kept."""
     power = np.asarray(power, dtype=np.float64)
     if power.ndim != 1 or power.size == 0:
         raise ValueError("power must be a non-empty vector, one value per cell")
@@ -56,7 +58,14 @@ def occupied(power, db, min_cells=1, lengths=None):
     if not np.all(lengths > 0):
         raise ValueError("cell lengths must be positive")
     density = power / lengths
-    keep = density >= float(np.median(density)) * 10.0 ** (float(db) / 10.0)
+    if floor is None:
+        keep = density >= float(np.median(density)) * 10.0 ** (float(db) / 10.0)
+    else:
+        floor = np.asarray(floor, dtype=np.float64)
+        if floor.shape != power.shape:
+            raise ValueError("floor: one value per cell (%d), not %s" % (power.size, floor.shape))
+        with np.errstate(invalid="ignore"):
+            keep = density >= floor / lengths * 10.0 ** (float(db) / 10.0)
     # run boundaries: where `keep` changes, with a closed cell assumed beyond both ends
     change = np.flatnonzero(np.diff(np.concatenate(([False], keep, [False])).astype(np.int8)))
     runs = []

@@ -14,6 +14,7 @@ import numpy as np
 
 from radiocore._internal import Injector, hip
 from radiocore.tools import iq, spectrum
+from radiocore.tools.floor import OverFloor, channel_noise_gain
 
 __all__ = ["Tuner", "Channel"]
 
@@ -27,6 +28,19 @@ _DEFAULT_OPTIONS = (True, True, True, 1, True)                         # set_ker
 # frames, the frame gate's uint8 [n, F + 1], or None (no gate was set).
 _Run = namedtuple("_Run", "blocks masks tones frames", defaults=(None, None, None, None))
 _FRAME_SCRATCH_BYTES = 256 << 20                                       # frame_levels: the most channel IQ held at a time
+
+
+class _Part:
+    """Elements [first, first + count) of a float32 device tensor, where a whole tensor of thresholds is expected."""
+
+    def __init__(self, whole, first, count):
+        self._whole, self._first, self._count = whole, first, count
+
+    def data_ptr(self):
+        return self._whole.data_ptr() + 4 * self._first
+
+    def tensor(self):
+        return self._whole[self._first:self._first + self._count]
 
 
 def _key_agc(key):
@@ -86,13 +100,14 @@ class Tuner(Injector):
         self._kernel_options = _DEFAULT_OPTIONS
         self._taps = {}            # (B, R, f, taps) -> (channels it holds, batched subcarrier handle) of subcarrier()
         # The settings: host values, replaced by their set_* and never changed in place, so that a lane follows by identity.
-        self._squelch = None       # set_squelch: None (off) or float32 thresholds, 0-d (every channel) or [len(channels())]
+        self._squelch = None       # set_squelch: None (off), float32 thresholds, 0-d (every channel) or [len(channels())], or an OverFloor
         self._fine = None          # retune: None or int64 [len(channels())] bins each channel was moved up
         self._iq_balance = None    # set_iq_balance: None (off) or (mode, beta, dc_notch)
         self._tones = None         # set_tones: None (off) or (bank, want int32 [C] or None, ratio float32 [C] or None)
         self._afilt = None         # set_audio_filter: None (off) or (AudioFilter, uint8 [C] or None)
         self._blanker = None       # set_blanker: None (off) or (NoiseBlanker, in_place)
-        self._gate = None          # set_gate: None (off) or (FrameGate, open float32, close float32: 0-d or [len(channels())])
+        self._gate = None          # set_gate: None (off) or (FrameGate, open float32, close float32: 0-d or [len(channels())]; or two OverFloor)
+        self._floor = None         # set_floor: None (off) or the NoiseFloor
         # What is made FROM a setting -- device copies, "fits this launch plan", what the device handle was last told -- is
         # looked up with what it is made from (_derived) and made again when that differs: nothing invalidates it by hand.
         self._built = {}           # name -> (setting, channel-list version / launch-plan key / handle key, what was made)
@@ -100,6 +115,8 @@ class Tuner(Injector):
         # Device state that is no copy of a setting: the filter's, shared by a lane, and the blanker's, each lane's own.
         self._afilt_handles = {}   # (legs, A) -> (channels, AudioFilter, librcfm handle): the filter's states, by channel index
         self._gate_handles = {}    # A -> (channels, FrameGate, librcfm handle): the gate's states, by channel index, shared by a lane
+        self._floor_handles = {}   # buffer length n -> (NoiseFloor, librcfm handle): the tracked floor, shared by a lane
+        self._floor_out = None     # the last load with a floor set: (n, cells, power, floor, {db: thresholds [C]}) on the device, each lane's own
         self._frame_scratch = None # frame_levels: the channel IQ of a chunk, this device tuner's own (allocated by the first call, kept)
         self._blank_handles = {}   # buffer length n -> (the NoiseBlanker it was made by, librcfm handle): this device tuner's own scratch
         self._blank_scratch = None # the blanked copy of a caller's device tensor (buffer's dtype and size; allocated by the first such load)
@@ -145,6 +162,8 @@ class Tuner(Injector):
         self._lo = self._hi = self._bw_sum = None
         self._afilt_handles.clear()        # the audio filter's states belong to the channels
         self._gate_handles.clear()         # ... and so do the frame gate's
+        self._floor_handles.clear()        # the tracked floor goes with the band
+        self._floor_out = None
         self._recalculate()
 
     def _recalculate(self, added=None):
@@ -272,6 +291,8 @@ class Tuner(Injector):
     def _load(self, x, n, whole, call, fmt, given):
         # what load and load_raw share: `call(handle, buffer)` is the library's load of a device buffer of n samples -- x,
         # or what the blanker made of it
+        if self._floor is not None:
+            self._floor_whole("load")
         h = self._device_tuner(n)
         if self._blanker is not None:
             x = self._blank(x, n, fmt, self._is_upload(given, x))
@@ -286,6 +307,9 @@ class Tuner(Injector):
             hip.check(call(h, x))
         self._input = x            # keeps the buffer alive until the FFT has consumed it
         self._loaded_size = n
+        self._floor_out = None
+        if self._floor is not None:
+            self._floor_pass(h, n)
 
     # ---- the spectrum as an object that can travel (rcfm_tuner_attach_spectrum / _window / _adopt) ---------------
 
@@ -597,6 +621,134 @@ class Tuner(Injector):
                                              hip.stream()))
         return dst
 
+    # ---- noise floor (rcfm_floor_run / rcfm_floor_thresholds behind the load; no reference counterpart) ------------------
+
+    def set_floor(self, nf=None):
+        """A noise floor that follows the band: with a ``radiocore.NoiseFloor``, every ``load`` / ``load_raw`` (and
+        ``Lanes.submit``) queues three calls behind the wideband FFT and the IQ balance, on the caller's stream and without
+        a host synchronisation: the power spectrum of the whole band in the floor's cells, the floor's order statistic and
+        smoothing (its state is one per cell and buffer length, carried from buffer to buffer), and the thresholds of
+        every channel -- the floor of the cell that holds the channel's centre, scaled to what ``levels()`` reads of white
+        noise of that density in the channel's bandwidth.  ``set_squelch(OverFloor(db))`` and ``set_gate(gate,
+        open=OverFloor(db))`` then compare against them; ``floor()``, ``floor_levels()`` and ``occupied_cells(db)`` read
+        the last load's.  The state is zeroed ("not primed": the next buffer's estimate is taken as it is) by
+        ``reset_states()`` and dropped by ``reset()`` and by another NoiseFloor.  ``None`` (the default) turns it off:
+        nothing more is launched than before.  Needs the whole spectrum: ValueError here, or RuntimeError in ``load``, on a
+        sharded tuner or with a spectrum or window attached.  ValueError for ``None`` while an ``OverFloor`` is in force, or
+        a floor with fewer than guard + 2 cells in this tuner's band; the setting in force stays."""
+        if nf is None:
+            if isinstance(self._squelch, OverFloor) or (self._gate is not None and isinstance(self._gate[1], OverFloor)):
+                raise ValueError("set_floor(None): an OverFloor threshold is in force (set_squelch / set_gate); turn it off first")
+        else:
+            if not hasattr(nf, "cells") or not hasattr(nf, "_create"):
+                raise ValueError("set_floor takes a radiocore.NoiseFloor")
+            try:
+                self._floor_whole("set_floor")
+            except RuntimeError as e:
+                raise ValueError(str(e))
+            if self._input_bandwidth and nf.cells(int(self._input_bandwidth)) < nf.guard + 2:
+                raise ValueError("set_floor: %d cells are fewer than guard + 2" % nf.cells(int(self._input_bandwidth)))
+        if nf is not self._floor:
+            self._floor_handles.clear()            # another floor: no cell is primed
+            self._floor_out = None
+        self._floor = nf
+
+    def _floor_whole(self, what):
+        if self._shard is not None or getattr(self, "_slot", None) is not None:
+            raise RuntimeError("%s: the noise floor needs the whole spectrum, not a shard's or an attached one" % what)
+
+    def _floor_dbs(self):
+        # the dB figures the load makes thresholds for: 0 (floor_levels) and whatever squelch and gate ask for
+        dbs = [0.0]
+        for a in (self._squelch,) + (tuple(self._gate[1:]) if self._gate is not None else ()):
+            if isinstance(a, OverFloor) and a.db not in dbs:
+                dbs.append(a.db)
+        return tuple(dbs)
+
+    def _floor_tables(self, n, dbs):
+        """(cell int32 [K C], gain float32 [K C]) on the device for the K figures of dbs, figure after figure: cell[c] is
+        the cell that holds the channel's centre bin (-1 when that lies outside the band: a NaN threshold, the channel stays
+        closed), gain[c] = G(B_c) / len(cell) 10^(db / 10) in float64, rounded once."""
+        def make():
+            C, M = len(self._bounds), self._floor.cells(n)
+            edges = spectrum.cell_edges(n, M)
+            centre = -np.array(list(self._rolls(self._fine)), dtype=np.int64) + n // 2      # span position of every centre bin
+            inside = (centre >= 0) & (centre < n)
+            cell = np.where(inside, np.searchsorted(edges, centre, side="right") - 1, -1).astype(np.int32)
+            width = np.diff(edges)[np.clip(cell, 0, M - 1)].astype(np.float64)
+            gains = {}
+            G = np.array([gains.setdefault(B, channel_noise_gain(B, n)) for B in (int(ch.bandwidth) for ch in self._bounds)])
+            gain = np.concatenate([(G / width * 10.0 ** (db / 10.0)).astype(np.float32) for db in dbs]) if C else np.zeros(0, np.float32)
+            return hip.to_device(np.tile(cell, len(dbs)), self._torch.int32), hip.to_device(gain, self._torch.float32)
+        fine = None if self._fine is None else self._fine.tobytes()
+        return self._derived("floor tables %r" % (dbs,), self._floor, (self._version, n, fine), make)
+
+    def _floor_handle(self, n):
+        # one handle per buffer length, shared with the lanes: the tracked floor is the band's, whoever loads the buffer
+        nf = self._floor
+        ent = self._floor_handles.get(n)
+        if ent is None or ent[0] is not nf:
+            h = nf._create(nf.cells(n))
+            if self._state_fence:
+                hip.check(self._lib.rcfm_floor_set_fence(h.value, 1))
+            ent = self._floor_handles[n] = (nf, h)
+        return ent[1].value
+
+    def _floor_pass(self, handle, n):
+        # behind the load (FFT and IQ balance) on the same stream: power spectrum, floor, thresholds
+        M = self._floor.cells(n)
+        t, s = self._torch, hip.stream()
+        power, floor = hip.empty((M,), t.float32), hip.empty((M,), t.float32)
+        hip.check(self._lib.rcfm_tuner_power_spectrum(handle, -(n // 2), n, M, hip.ptr(power), None, s))
+        hip.check(self._lib.rcfm_floor_run(self._floor_handle(n), hip.ptr(power), 1.0, hip.ptr(floor), None, s))
+        self._floor_out = (n, M, power, floor, {})
+        self._floor_queue(self._floor_dbs())
+
+    def _floor_queue(self, dbs):
+        # rcfm_floor_thresholds of the last load's floor for every figure of dbs, one call
+        n, M, _, floor, held = self._floor_out
+        C = len(self._bounds)
+        cell, gain = self._floor_tables(n, dbs)
+        thr = hip.empty((len(dbs) * C,), self._torch.float32)
+        hip.check(self._lib.rcfm_floor_thresholds(hip.ptr(floor), M, hip.ptr(cell), hip.ptr(gain), len(dbs) * C, hip.ptr(thr),
+                                                  hip.stream()))
+        for k, db in enumerate(dbs):
+            held[db] = _Part(thr, k * C, C)
+
+    def _floor_thresholds(self, db):
+        """The last load's thresholds ``db`` over the floor, float32 [len(channels())] on the device (a _Part): made by the
+        load for the figures in force then, and from its floor now for one that was set since."""
+        if self._floor is None or self._floor_out is None or self._floor_out[0] != self._loaded_size:
+            raise RuntimeError("an OverFloor threshold needs a load with the noise floor set (set_floor)")
+        held = self._floor_out[4]
+        if db not in held:
+            self._floor_queue((db,))
+        return held[db]
+
+    def _floor_read(self, what):
+        if self._floor_out is None:
+            raise RuntimeError("%s: no load with a noise floor set (set_floor) yet" % what)
+        return self._floor_out
+
+    def floor(self, numpy_output: bool = True):
+        """float32 [cells]: the tracked noise floor of every cell after this tuner's last ``load`` with a floor set, in the
+        units of ``power_spectrum(cells)`` -- power per cell."""
+        return self._out(self._floor_read("floor")[3], numpy_output)
+
+    def floor_levels(self, numpy_output: bool = True):
+        """float32 [len(channels())]: what ``levels()`` would read of every channel if it held nothing but the noise floor
+        of its cell -- ``OverFloor(0)``."""
+        self._floor_read("floor_levels")
+        return self._out(self._floor_thresholds(0.0).tensor(), numpy_output)
+
+    def occupied_cells(self, db):
+        """numpy bool [cells]: the cells of the last load whose power is at least ``db`` dB over their tracked floor -- the
+        rule of rcfm_floor_run's ``over``, ``power >= float32(10 ** (db / 10)) * floor`` in float32, false on NaN."""
+        _, _, power, floor, _ = self._floor_read("occupied_cells")
+        ratio = np.float32(10.0 ** (float(db) / 10.0))
+        with np.errstate(invalid="ignore"):
+            return hip.to_host(power) >= ratio * hip.to_host(floor)
+
     def set_squelch(self, threshold=None):
         """Mute what is below a level: from now on ``run_all`` / ``run_each`` (and ``Lanes.submit``) compare every
         channel's level of the buffer with its threshold -- a scalar, or a sequence of ``len(channels())``, in the units
@@ -604,12 +756,19 @@ class Tuner(Injector):
         decision is per buffer, on the device and on the caller's stream (no host synchronisation), and the
         demodulators still run on every channel: the de-emphasis state advances as without squelch.  A NaN threshold
         keeps a channel closed.  ``None`` (the default) turns squelch off: nothing more is launched than before.
-        ``squelch.threshold_over_floor`` derives thresholds from a ``levels()`` pass.  ValueError while a frame gate is set
-        (``set_gate``): the two take the same place."""
+        ``squelch.threshold_over_floor`` derives thresholds from a ``levels()`` pass; with a noise floor set (``set_floor``)
+        ``OverFloor(db)`` stands for "db over the floor at each channel, as the buffer's load tracked it" and needs no such
+        pass.  ValueError while a frame gate is set (``set_gate``): the two take the same place; and for an ``OverFloor``
+        without ``set_floor``; the setting in force stays."""
         if threshold is not None and self._gate is not None:
             raise ValueError("set_squelch: a frame gate is set (set_gate); turn it off first")
-        self._squelch = None if threshold is None else self._per_channel(        # (np.array: a copy, a new object per setting)
-            np.array(threshold, dtype=np.float32), "squelch thresholds: a scalar or one per channel")
+        if isinstance(threshold, OverFloor):
+            if self._floor is None:
+                raise ValueError("set_squelch: OverFloor needs a noise floor (set_floor)")
+            self._squelch = OverFloor(threshold.db)                                # (a new object per setting)
+        else:
+            self._squelch = None if threshold is None else self._per_channel(    # (np.array: a copy, a new object per setting)
+                np.array(threshold, dtype=np.float32), "squelch thresholds: a scalar or one per channel")
         self._last = self._last._replace(masks=None)
 
     def open_mask(self):
@@ -836,7 +995,8 @@ class Tuner(Injector):
         behind the tone bank and the audio filter, ahead of the tone squelch.  ``open_mask()`` tells which channels had
         anything open in the buffer (``run_all_packed``, the ``Drain`` and ``wire.frames_packed`` work on it unchanged),
         ``frame_mask()`` which frames.  ``open`` and ``close``: in the units of ``levels()``, a scalar or one per channel
-        (``squelch.threshold_over_floor`` gives ``open``); ``close`` defaults to ``open`` lowered by ``hysteresis_db``.  The
+        (``squelch.threshold_over_floor`` gives ``open``), or -- with ``set_floor`` -- ``OverFloor(db)`` for both, the
+        thresholds the buffer's load made from the tracked noise floor; ``close`` defaults to ``open`` lowered by ``hysteresis_db``.  The
         state is one per channel, carried from buffer to buffer, kept when channels are added, zeroed by ``reset_states()``
         and dropped by ``reset()`` and by another gate.  ``None`` (the default) turns it off: nothing more is launched than
         before.  ValueError -- the setting in force stays -- for ``close`` above ``open``, while ``set_squelch`` is set, and,
@@ -855,13 +1015,23 @@ class Tuner(Injector):
             if open is None:
                 raise ValueError("set_gate: a gate needs its open threshold")
             what = "gate thresholds: a scalar or one per channel"
-            o = self._per_channel(np.array(open, dtype=np.float32), what)
-            if close is None:
-                c = (o.astype(np.float64) * 10.0 ** (-float(hysteresis_db) / 10.0)).astype(np.float32)
+            if isinstance(open, OverFloor) or isinstance(close, OverFloor):
+                if self._floor is None:
+                    raise ValueError("set_gate: OverFloor needs a noise floor (set_floor)")
+                if not isinstance(open, OverFloor) or not (close is None or isinstance(close, OverFloor)):
+                    raise ValueError("set_gate: open and close are both levels or both OverFloor")
+                o = OverFloor(open.db)
+                c = OverFloor(open.db - float(hysteresis_db) if close is None else close.db)
+                if c.db > o.db:
+                    raise ValueError("set_gate: close lies above open")
             else:
-                c = self._per_channel(np.array(close, dtype=np.float32), what)
-            if np.any(c > o):
-                raise ValueError("set_gate: close lies above open")
+                o = self._per_channel(np.array(open, dtype=np.float32), what)
+                if close is None:
+                    c = (o.astype(np.float64) * 10.0 ** (-float(hysteresis_db) / 10.0)).astype(np.float32)
+                else:
+                    c = self._per_channel(np.array(close, dtype=np.float32), what)
+                if np.any(c > o):
+                    raise ValueError("set_gate: close lies above open")
             setting = (gate, o, c)
             self._fit_gate(setting)                # refused here, with the old setting still in force
             if self._gate is None or self._gate[0] is not gate:
@@ -878,7 +1048,7 @@ class Tuner(Injector):
         def check():
             gate, C = setting[0], len(self._bounds)
             for a in setting[1:]:
-                if a.ndim == 1 and a.shape[0] != C:
+                if not isinstance(a, OverFloor) and a.ndim == 1 and a.shape[0] != C:
                     raise ValueError("gate thresholds were set for %d channels, the tuner has %d" % (a.shape[0], C))
             for g in self._launch_plan()[0]:
                 if g[2] is not None:
@@ -924,7 +1094,10 @@ class Tuner(Injector):
         def upload():
             C = len(self._bounds)
             return tuple(hip.to_device(np.array(np.broadcast_to(a, (C,))), self._torch.float32) for a in self._gate[1:])    # (a copy: writable)
-        thr_open, thr_close = self._derived("gate thresholds", self._gate, self._version, upload)
+        if isinstance(self._gate[1], OverFloor):
+            thr_open, thr_close = self._floor_thresholds(self._gate[1].db), self._floor_thresholds(self._gate[2].db)
+        else:
+            thr_open, thr_close = self._derived("gate thresholds", self._gate, self._version, upload)
         F = self._gate[0].frames
         A, ch = int(audio.shape[1]), int(audio.shape[2])
         t = self._torch
@@ -963,7 +1136,10 @@ class Tuner(Injector):
                                  % (a.shape[0], len(self._bounds)))
             full = np.ascontiguousarray(np.broadcast_to(a, (len(self._bounds),)))
             return hip.to_device(full, self._torch.float32)
-        thr = self._derived("squelch", self._squelch, self._version, upload)
+        if isinstance(self._squelch, OverFloor):
+            thr = self._floor_thresholds(self._squelch.db)
+        else:
+            thr = self._derived("squelch", self._squelch, self._version, upload)
         power = hip.empty((count,), self._torch.float32)
         mask = hip.empty((count,), self._torch.uint8)
         s = hip.stream()
@@ -1145,6 +1321,8 @@ class Tuner(Injector):
             hip.check(self._lib.rcfm_audio_filter_reset(h.value, hip.stream()))
         for _, _, h in self._gate_handles.values():
             hip.check(self._lib.rcfm_gate_reset(h.value, hip.stream()))
+        for _, h in self._floor_handles.values():
+            hip.check(self._lib.rcfm_floor_reset(h.value, hip.stream()))
 
     def set_kernel_options(self, lds_chain=True, fused_tiles=True, phase_link=True, narrow_tiles=1, ssb_direct=True):
         """Which forms of the kernel chain run_all / run_each may use (rcfm_demod_set_option; no reference
@@ -1228,6 +1406,8 @@ class Tuner(Injector):
             hip.check(self._lib.rcfm_audio_filter_set_fence(h.value, 1))
         for _, _, h in self._gate_handles.values():
             hip.check(self._lib.rcfm_gate_set_fence(h.value, 1))
+        for _, h in self._floor_handles.values():
+            hip.check(self._lib.rcfm_floor_set_fence(h.value, 1))
 
     def _lane_clone(self):
         """A second Tuner over the SAME channel list, demodulator objects and de-emphasis state, with its own device
@@ -1238,7 +1418,8 @@ class Tuner(Injector):
         t._state_fence = True
         t._state_owner = self._state_owner        # shared, the same dicts: one de-emphasis state per channel, whoever runs it ...
         t._afilt_handles = self._afilt_handles    # ... and one audio filter state ...
-        t._gate_handles = self._gate_handles      # ... and one frame gate state; every other device handle is the lane's own
+        t._gate_handles = self._gate_handles      # ... and one frame gate state ...
+        t._floor_handles = self._floor_handles    # ... and one tracked noise floor; every other device handle is the lane's own
         t._sync_lane(self)
         return t
 
@@ -1249,8 +1430,10 @@ class Tuner(Injector):
             self._last = _Run()                            # (Lanes keeps each buffer's results with its ticket)
         if self._blanker is not base._blanker:
             self.set_blanker(None)                         # the handle and scratch of this lane's own go with their blanker
-        self._squelch, self._tones, self._afilt, self._iq_balance, self._blanker, self._fine, self._gate = \
-            base._squelch, base._tones, base._afilt, base._iq_balance, base._blanker, base._fine, base._gate
+        if self._floor is not base._floor:
+            self._floor_out = None                         # (the handles are shared: the base tuner's set_floor dropped them)
+        self._squelch, self._tones, self._afilt, self._iq_balance, self._blanker, self._fine, self._gate, self._floor = \
+            base._squelch, base._tones, base._afilt, base._iq_balance, base._blanker, base._fine, base._gate, base._floor
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
                 self._input_bandwidth == base._input_bandwidth:
             return
