@@ -76,7 +76,9 @@ def test_run_all_a_not_multiple_of_four(rc, oracle, kind, A):
     B = 60000 (pair FFT -> full spectrum -> unpack -> real-output inverse FFT); A = 12006 has the prime factors 23 and
     29: every transform of the demodulator goes through rocFFT.  For WBFM that is the only route with separate
     `hilbert_mask` and `stereo_mix` stages (rcfm_demod_s::run_wbfm_rocfft), and it leaves no DC bin, so the de-emphasis
-    runs unfused (generic FIR, then `dc_clip`) although A * 2 % 4 == 0: the stage profile must show that route ran."""
+    runs unfused (generic FIR, then `dc_clip`) although A * 2 % 4 == 0: the stage profile must show that route ran.
+    `dc_clip` alone does not mark it (the engine launches it too whenever A * ch % 4 != 0); tests/test_hip_lengths.py
+    runs the same route at odd, equal and up-sampling lengths."""
     from radiocore._internal import hip
     lib = hip.lib()
     N, B, C = 1_200_000, 60000, 3
