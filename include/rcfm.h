@@ -59,7 +59,8 @@ extern "C" {
                             rcfm_subcarrier_describe added to rcfm_tools.h (a new host-only symbol, nothing existing changed);
                             rcfm_blanker_* added, rcfm_blanker_last in rcfm_tools.h, RCFM_IQ_CF32 = 0 named (new symbols only,
                             nothing existing changed: the load entry points refuse format 0 as before);
-                            rcfm_rank_filter and rcfm_floor_* added (new symbols only, nothing existing changed) */
+                            rcfm_rank_filter and rcfm_floor_* added (new symbols only, nothing existing changed);
+                            rcfm_mix_* added (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -99,6 +100,7 @@ typedef struct rcfm_tone_bank_s* rcfm_tone_bank_t;
 typedef struct rcfm_audio_filter_s* rcfm_audio_filter_t;
 typedef struct rcfm_gate_s* rcfm_gate_t;
 typedef struct rcfm_floor_s* rcfm_floor_t;
+typedef struct rcfm_mix_s* rcfm_mix_t;
 typedef struct rcfm_resampler_s* rcfm_resampler_t;
 typedef struct rcfm_feeder_s* rcfm_feeder_t;
 typedef struct rcfm_comm_s* rcfm_comm_t;
@@ -724,6 +726,51 @@ int rcfm_floor_get_state(rcfm_floor_t h, float* state_host, void* stream);
 int rcfm_floor_set_state(rcfm_floor_t h, const float* state_host, void* stream);
 int rcfm_floor_set_fence(rcfm_floor_t h, int on);
 int rcfm_floor_destroy(rcfm_floor_t h);
+
+/* ---- audio buses: the open channels mixed to a few mono or stereo streams (no reference counterpart) -----------------------
+ * Hundreds of channel rows can be recorded, not listened to: a band monitor is heard through a few mixed outputs ("tower +
+ * ground + approach on one stream, everything else on a second"), every member at its own gain and spread from left to right
+ * so that two talkers who overlap stay separable.  The mixer adds the open rows up on the device; its output is one more
+ * [rows][A ch] block with a mask, which rcfm_audio_pack and the drain take as they take the channel rows.
+ *
+ * Definition.  A mixer has M buses, 1 <= M <= 1024.  Bus m owns routes j = bus_start[m] .. bus_start[m + 1] - 1; a bus may be
+ * empty and has at most 65 535 routes; R = bus_start[M] <= 2^20 routes in all.  Route j has a channel index c_j and two
+ * float32 gains (gl_j, gr_j), finite.  A channel appears at most once per bus, and in any number of buses.
+ * Input: audio [count][A][ch_in] float32, the channels [first, first + count), ch_in 1 or 2; open [count] uint8 as
+ * rcfm_squelch / rcfm_gate_run write it, any nonzero byte is open, NULL: every channel is open.
+ * Output: out [M][A][ch_out] float32, ch_out 1 or 2; active [M] int32, the number of open routes of each bus; bus_open [M]
+ * uint8, 1 where active > 0, else 0.  active and bus_open may be NULL.
+ *
+ * Terms.  Every product and every sum is one float32 operation, round to nearest, never contracted to an fma: (x) is
+ * __fmul_rn, (+) is __fadd_rn.  With x^L, x^R the first and the last leg of the row's sample (the same leg when ch_in = 1):
+ *   ch_out = 2:              t^L = gl (x) x^L,  t^R = gr (x) x^R
+ *   ch_out = 1, ch_in = 1:   t = gl (x) x
+ *   ch_out = 1, ch_in = 2:   t = (gl (x) x^L) (+) (gr (x) x^R)
+ *
+ * Order.  It depends on the bus's route list alone -- never on the mask, the device, the launch or the alignment.  The
+ * routes of a bus are cut by position into segments of 16 consecutive routes (the last may be shorter).  Segment sum:
+ * s_k = (..((+0 (+) t_a) (+) t_b)..) over the OPEN routes of segment k in route order.  Output: out = (..((+0 (+) s_0) (+)
+ * s_1)..) over all segments in order; a segment with no open route contributes +0.  The rows of a closed route are not read:
+ * a NaN in a closed row reaches no output.  A bus with no open route, or with no route at all, gets a row of +0.  The
+ * segments are there so that a long route list can be spread over waves; how the work is dealt out is the implementation's
+ * choice, the order is not.  No atomics: the output bits are the same from run to run, from stream to stream, and whatever
+ * the 4- or 16-byte alignment of audio and out.
+ *
+ * create    bus_start_host [M + 1], route_channel_host [R], route_gain_host [R][2] (gl, gr); the handle keeps a host copy and
+ *           a device copy of the tables, the latter plain device memory that never comes from a bound arena.  It holds no
+ *           state across buffers: any number of streams may run it without a fence.  RCFM_ERR_ARG before any device call: a
+ *           NULL pointer, M outside 1 .. 1024, ch_out outside {1, 2}, bus_start[0] != 0, a bus_start that decreases, a bus of
+ *           more than 65 535 routes, R > 2^20, a negative channel index, a channel twice in one bus, a gain that is not finite.
+ * run       One kernel, asynchronous on `stream`, no device allocation, no host synchronisation.  RCFM_ERR_ARG before any
+ *           device call: a NULL handle, audio or out, ch_in outside {1, 2}, count < 1, A < 1, audio or out not aligned for a
+ *           float (active: for an int32), out overlapping audio.  RCFM_ERR_INDEX when a route's channel lies outside
+ *           [first, first + count): the host copy decides, nothing is launched.
+ * destroy   NULL is accepted. */
+int rcfm_mix_create(int M, const int32_t* bus_start_host, const int32_t* route_channel_host,
+                    const float* route_gain_host /* [R][2] */, int ch_out, rcfm_mix_t* out);
+int rcfm_mix_run(rcfm_mix_t h, int first, int count, int A, int ch_in, const void* audio, const void* open, void* out,
+                 void* active, void* bus_open, void* stream);
+int rcfm_mix_destroy(rcfm_mix_t h);
 
 /* ---- noise blanker: impulse noise removed from the wideband buffer, ahead of the FFT (no reference counterpart) -----------
  * A pulse of a few samples (ignition, switching supplies, electric fences) is white across the band: after rcfm_tuner_load it

@@ -19,4 +19,5 @@ from radiocore.tools.audiofilter import *
 from radiocore.tools.blanker import *
 from radiocore.tools.gate import *
 from radiocore.tools.floor import *
+from radiocore.tools.mix import *
 from radiocore.tools import iq, rds, tones, audiofilter

@@ -101,12 +101,13 @@ class Lanes:
         return float(start.elapsed_time(end))
 
     def result(self, ticket: int, numpy_output: bool = True, open_mask: bool = False, tones: bool = False,
-               frame_mask: bool = False):
+               frame_mask: bool = False, mix: bool = False):
         """The audio of one submitted buffer, [C, A, ch] float32 (the shard's block after Tuner.shard).
         open_mask=True: ``(audio, mask)`` with the squelch's numpy bool [C] of that buffer (Tuner.open_mask; None when
         the buffer was submitted with squelch off).  frame_mask=True: the frame gate's numpy bool [C, frames] of that
         buffer follows (Tuner.frame_mask; None when it was submitted without a gate).  tones=True: the tone bank's
-        ``(P, E)`` of that buffer (Tuner.tone_power; None when it was submitted without a bank) comes last in the tuple."""
+        ``(P, E)`` of that buffer (Tuner.tone_power; None when it was submitted without a bank) follows.  mix=True: the
+        buffer's buses (Tuner.mix; None when it was submitted without a mixer) come last in the tuple."""
         entry = self._pending.pop(ticket)
         run = entry.run
         device_output = self._base._cuda and not numpy_output
@@ -130,6 +131,11 @@ class Lanes:
                     p.record_stream(cur)
                     e.record_stream(cur)
             extra.append(self._base._tone_result(run.tones, device_output) if run.tones is not None else None)
+        if mix:
+            if device_output and run.mix is not None:
+                for o, _, _ in run.mix[1]:
+                    o.record_stream(cur)
+            extra.append(self._base._mix_result(run.mix, device_output) if run.mix is not None else None)
         return (out, *extra) if extra else out
 
     def hold_current_stream(self, ticket: int):

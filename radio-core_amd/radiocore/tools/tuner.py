@@ -25,8 +25,9 @@ _STATELESS = (hip.RCFM_FM, hip.RCFM_AM, hip.RCFM_USB, hip.RCFM_LSB)    # kinds w
 _DEFAULT_OPTIONS = (True, True, True, 1, True)                         # set_kernel_options: lds_chain, fused_tiles, phase_link, narrow_tiles, ssb_direct
 # What one run_all / run_each queued, on the device, one entry per launch group: blocks [(n, ch, audio [n, A, ch])]; masks, the
 # squelch's uint8 [n], or None (no squelch was set, or nothing was gated); tones, the bank's (P, E), or None (no bank was set);
-# frames, the frame gate's uint8 [n, F + 1], or None (no gate was set).
-_Run = namedtuple("_Run", "blocks masks tones frames", defaults=(None, None, None, None))
+# frames, the frame gate's uint8 [n, F + 1], or None (no gate was set).  mix, not per group: None (no mixer was set) or
+# (owner [M], the group each bus belongs to, [(out [M, A, ch_out], active int32 [M], bus_open uint8 [M]) per group]).
+_Run = namedtuple("_Run", "blocks masks tones frames mix", defaults=(None, None, None, None, None))
 _FRAME_SCRATCH_BYTES = 256 << 20                                       # frame_levels: the most channel IQ held at a time
 
 
@@ -108,6 +109,7 @@ class Tuner(Injector):
         self._blanker = None       # set_blanker: None (off) or (NoiseBlanker, in_place)
         self._gate = None          # set_gate: None (off) or (FrameGate, open float32, close float32: 0-d or [len(channels())]; or two OverFloor)
         self._floor = None         # set_floor: None (off) or the NoiseFloor
+        self._mix = None           # set_mix: None (off) or the Mixer
         # What is made FROM a setting -- device copies, "fits this launch plan", what the device handle was last told -- is
         # looked up with what it is made from (_derived) and made again when that differs: nothing invalidates it by hand.
         self._built = {}           # name -> (setting, channel-list version / launch-plan key / handle key, what was made)
@@ -117,6 +119,7 @@ class Tuner(Injector):
         self._gate_handles = {}    # A -> (channels, FrameGate, librcfm handle): the gate's states, by channel index, shared by a lane
         self._floor_handles = {}   # buffer length n -> (NoiseFloor, librcfm handle): the tracked floor, shared by a lane
         self._floor_out = None     # the last load with a floor set: (n, cells, power, floor, {db: thresholds [C]}) on the device, each lane's own
+        self._mix_handles = {}     # the launch groups ((first, count), ..) -> (Mixer, channel-list version, owner [M], librcfm handle per group): no state, shared by a lane
         self._frame_scratch = None # frame_levels: the channel IQ of a chunk, this device tuner's own (allocated by the first call, kept)
         self._blank_handles = {}   # buffer length n -> (the NoiseBlanker it was made by, librcfm handle): this device tuner's own scratch
         self._blank_scratch = None # the blanked copy of a caller's device tensor (buffer's dtype and size; allocated by the first such load)
@@ -164,6 +167,7 @@ class Tuner(Injector):
         self._gate_handles.clear()         # ... and so do the frame gate's
         self._floor_handles.clear()        # the tracked floor goes with the band
         self._floor_out = None
+        self._mix_handles.clear()          # the mixer's tables name channels of the list that goes
         self._recalculate()
 
     def _recalculate(self, added=None):
@@ -1111,6 +1115,94 @@ class Tuner(Injector):
         hip.check(self._lib.rcfm_gate_apply(g, hip.ptr(fmask), count, F, A, ch, hip.ptr(audio), s))
         return mask, fmask
 
+    # ---- audio buses (rcfm_mix_run behind everything else of a group; no reference counterpart) -------------------------
+
+    def set_mix(self, mixer=None):
+        """The open channels mixed to a few streams: with a ``radiocore.Mixer``, ``run_all`` / ``run_each`` /
+        ``run_all_packed`` (and ``Lanes.submit``) queue the mixer behind everything else of each group -- the tone bank, the
+        audio filter, the level squelch or the frame gate, the tone squelch -- on their final open mask, on the caller's
+        stream and without a host synchronisation: every bus is the sum of its open channels' audio at the routes' gains,
+        in the one order the route list fixes (include/rcfm.h, "audio buses"); a closed channel is not read.  ``mix()``
+        returns the buses of the last run, ``mix_active()`` how many channels each had open, and
+        ``run_all_packed(pcm, drain=..., buses=True)`` packs and drains the bus rows instead of the channel rows.  The
+        channel audio itself is what it is without a mixer.  ``run_each`` mixes per group of like channels: a bus takes
+        channels of one group, and buses of different groups may differ in length.  Routes name channel indices, so a
+        channel list that grows keeps working.  ``None`` (the default) turns it off: nothing more is launched than before.
+        ValueError -- the setting in force stays -- for anything but a Mixer, for a route to a channel the tuner does not
+        have (here, and in a run after ``reset()``, before anything is launched), for a bus across two groups (in
+        ``run_each``, before anything is launched), on a sharded tuner or with a spectrum or window attached."""
+        if mixer is not None:
+            if not hasattr(mixer, "buses") or not hasattr(mixer, "_split"):
+                raise ValueError("set_mix takes a radiocore.Mixer")
+            try:
+                self._mix_whole("set_mix")
+            except RuntimeError as e:
+                raise ValueError(str(e))
+            if self._bounds and mixer.highest_channel() >= len(self._bounds):
+                raise ValueError("set_mix: a route names channel %d, the tuner has %d channels"
+                                 % (mixer.highest_channel(), len(self._bounds)))
+        if mixer is not self._mix:
+            self._mix_handles.clear()              # another mixer: other tables
+        self._mix = mixer
+        self._last = self._last._replace(mix=None)
+
+    def _mix_whole(self, what):
+        if self._shard is not None or getattr(self, "_slot", None) is not None:
+            raise RuntimeError("%s: the mixer takes every channel of the tuner, not a shard's or an attached window's" % what)
+
+    def _fit_mix(self, ranges):
+        """(owner [M], [librcfm handle per group]) of the mixer for the launch groups ``ranges`` ((first, count), ..): made
+        once per mixer, channel-list version and grouping, before a run has launched anything -- whatever is wrong with the
+        routes for these channels raises here."""
+        self._mix_whole("run")
+        mixer = self._mix
+        ent = self._mix_handles.get(ranges)
+        if ent is None or ent[0] is not mixer or ent[1] != self._version:
+            owner, tables = mixer._split(ranges, len(self._bounds))
+            for key in [k for k, e in self._mix_handles.items() if e[1] != self._version]:
+                del self._mix_handles[key]         # the handles of a channel list that is gone
+            ent = self._mix_handles[ranges] = (mixer, self._version, owner, [mixer._create(*t) for t in tables])
+        return ent[2], [h.value for h in ent[3]]
+
+    def _mix_group(self, h, first, count, audio, mask):
+        # behind the group's squelch / gate / tone squelch on the same stream, on their final mask (None: every channel open)
+        M, ch_out = self._mix.M, self._mix.ch_out
+        A, ch = int(audio.shape[1]), int(audio.shape[2])
+        t = self._torch
+        out = hip.empty((M, A, ch_out), t.float32)
+        active = hip.empty((M,), t.int32)
+        bus_open = hip.empty((M,), t.uint8)
+        hip.check(self._lib.rcfm_mix_run(h, first, count, A, ch, hip.ptr(audio), hip.ptr(mask) if mask is not None else None,
+                                         hip.ptr(out), hip.ptr(active), hip.ptr(bus_open), hip.stream()))
+        return out, active, bus_open
+
+    def mix(self, numpy_output: bool = True):
+        """The buses of this tuner's last ``run_all`` / ``run_each`` / ``run_all_packed`` with a mixer set, float32
+        [M, A, ch_out].  After a ``run_each`` over several groups: a list with one [A, ch_out] array per bus (the groups'
+        audio lengths may differ; a bus without a route has the first group's)."""
+        if self._last.mix is None:
+            raise RuntimeError("mix: no run_all / run_each with a mixer set (set_mix) yet")
+        return self._mix_result(self._last.mix, self._cuda and not numpy_output)
+
+    def _mix_result(self, mix, device_output):
+        owner, groups = mix
+        if len(groups) == 1:
+            return self._result(groups[0][0], device_output)
+        outs = [self._result(g[0], device_output) for g in groups]
+        return [outs[k][m] for m, k in enumerate(owner)]
+
+    def mix_active(self):
+        """numpy int32 [M]: how many routes of each bus were open in this tuner's last run with a mixer set."""
+        if self._last.mix is None:
+            raise RuntimeError("mix_active: no run_all / run_each with a mixer set (set_mix) yet")
+        return self._mix_active_result(self._last.mix)
+
+    @staticmethod
+    def _mix_active_result(mix):
+        owner, groups = mix
+        active = [np.asarray(hip.to_host(g[1])) for g in groups]
+        return np.array([active[k][m] for m, k in enumerate(owner)], dtype=np.int32)
+
     def _gates(self, handle, first, count, audio):
         """What follows a group's rcfm_pipeline_run on the same stream: the tone bank, the audio filter, the level squelch
         or the frame gate, the tone squelch, each only when set.  (tones (P, E) or None, open mask or None, frame mask or None)."""
@@ -1201,9 +1293,11 @@ class Tuner(Injector):
         self._fit_tones(self._tones)
         self._fit_afilt(self._afilt)
         self._fit_gate(self._gate)
+        owner, mixes = self._fit_mix(tuple((g[0], g[1]) for g in groups)) if self._mix is not None else (None, None)
         gated = self._squelch is not None or self._gate is not None or (self._tones is not None and self._tones[1] is not None)
-        run = _Run([], [] if gated else None, [] if self._tones is not None else None, [] if self._gate is not None else None)
-        for first, count, kind, B, A, tau, *agc in groups:
+        run = _Run([], [] if gated else None, [] if self._tones is not None else None, [] if self._gate is not None else None,
+                   (owner, []) if mixes is not None else None)
+        for k, (first, count, kind, B, A, tau, *agc) in enumerate(groups):
             ch = 2 if kind == hip.RCFM_WBFM else 1
             audio = hip.empty((count, A, ch), self._torch.float32)
             hip.check(self._lib.rcfm_pipeline_run(handle, self._batched_demod(kind, B, A, tau, chunk, *agc), first, count,
@@ -1219,10 +1313,12 @@ class Tuner(Injector):
                 run.tones.append(tones)
             if run.frames is not None:
                 run.frames.append(frames)
-        self._last = _Run(None, run.masks, run.tones, run.frames)
+            if run.mix is not None:
+                run.mix[1].append(self._mix_group(mixes[k], first, count, audio, mask))
+        self._last = _Run(None, run.masks, run.tones, run.frames, run.mix)
         return run
 
-    def run_all_packed(self, pcm, numpy_output: bool = True, chunk: int = 0, drain=None):
+    def run_all_packed(self, pcm, numpy_output: bool = True, chunk: int = 0, drain=None, buses: bool = False):
         """``run_all`` for a publisher (rcfm_audio_pack; no reference counterpart): the audio of the OPEN channels only,
         packed densely in channel order in the sample format of ``pcm`` (a ``radiocore.PCM``: int16 at a gain, or float32
         unchanged).  The launches of ``run_all`` run unchanged -- squelch included when set, and ``open_mask()`` keeps
@@ -1235,22 +1331,32 @@ class Tuner(Injector):
         With ``drain`` (a ``radiocore.tools.Drain`` of at least ``count`` rows of [A, ch] in pcm's dtype): the packed audio
         goes into the drain's next free slot and its header's copy is queued; the call returns nothing and does not
         wait -- ``drain.next()`` hands the buffer out.  RuntimeError when every slot of the drain is in flight, ValueError
-        for a drain of another geometry: both before anything is launched."""
+        for a drain of another geometry: both before anything is launched.
+        ``buses=True`` (with a mixer set, ``set_mix``): the same for the bus rows instead of the channel rows -- the M buses
+        of [A, ch_out], a bus being open when one of its channels is; ``index`` then counts buses, and a drain holds at
+        least M rows of [A, ch_out].  ValueError without a mixer."""
         self._ready()
         count, geo = self._launch_plan()[2], self._plan_uniform()
         if count < 1:
             raise ValueError("run_all_packed needs at least one channel")
+        if buses:
+            if self._mix is None:
+                raise ValueError("run_all_packed(buses=True) needs a mixer (set_mix)")
+            count = self._mix.M
         if drain is not None and geo is not None:          # refused before anything runs (a run advances the de-emphasis state)
-            shape = (geo[2], 2 if geo[0] == hip.RCFM_WBFM else 1)
+            shape = (geo[2], self._mix.ch_out) if buses else (geo[2], 2 if geo[0] == hip.RCFM_WBFM else 1)
             if drain.rows < count or drain.row_shape != shape or drain.dtype != pcm.dtype:
                 raise ValueError("the drain holds %d rows of %s %s, this run packs %d rows of %s %s"
                                  % (drain.rows, drain.row_shape, drain.dtype, count, shape, pcm.dtype))
         if drain is not None:
             packed, index, n_open = drain._begin()         # ... and so is a drain with every slot in flight
         run = self._run_all_device(chunk)
-        audio = run.blocks[0][2]
+        if buses:
+            audio, _, mask = run.mix[1][0]
+        else:
+            audio = run.blocks[0][2]
+            mask = run.masks[0] if run.masks else None
         row = int(audio.shape[1]) * int(audio.shape[2])
-        mask = run.masks[0] if run.masks else None
         args = (hip.ptr(audio), hip.ptr(mask) if mask is not None else None, count, row, pcm.format, pcm.gain)
         if drain is not None:
             hip.check(self._lib.rcfm_audio_pack(*args, packed, index, n_open, hip.stream()))
@@ -1419,15 +1525,18 @@ class Tuner(Injector):
         t._state_owner = self._state_owner        # shared, the same dicts: one de-emphasis state per channel, whoever runs it ...
         t._afilt_handles = self._afilt_handles    # ... and one audio filter state ...
         t._gate_handles = self._gate_handles      # ... and one frame gate state ...
-        t._floor_handles = self._floor_handles    # ... and one tracked noise floor; every other device handle is the lane's own
+        t._floor_handles = self._floor_handles    # ... and one tracked noise floor ...
+        t._mix_handles = self._mix_handles        # ... and the mixer's tables, which hold no state; every other device handle is the lane's own
         t._sync_lane(self)
         return t
 
     def _sync_lane(self, base):
         """Follow the base tuner: its settings, each a new object per set_* -- what this lane made from the old one is made
         again when it is next used (_derived), on the lane's own stream -- and its channel list."""
-        if self._tones is not base._tones or self._squelch is not base._squelch or self._gate is not base._gate:
+        if self._tones is not base._tones or self._squelch is not base._squelch or self._gate is not base._gate or \
+                self._mix is not base._mix:
             self._last = _Run()                            # (Lanes keeps each buffer's results with its ticket)
+        self._mix = base._mix
         if self._blanker is not base._blanker:
             self.set_blanker(None)                         # the handle and scratch of this lane's own go with their blanker
         if self._floor is not base._floor:
