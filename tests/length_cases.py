@@ -177,11 +177,19 @@ def phase_capable(kind, B, plans_B):
 # k_stereo_unpack as the audio_spectrum stage; "ifft_load": LoadStereoUnpack on the first pass of IFFT_A (WBFM on the
 # engine has no audio_spectrum stage: the ifft_A stage marks it).  The GPU test reads the site from the stage profile and
 # holds it to this: a case that moves between the tile and a separate resample is noticed.
-TILE_CASES = {("WBFM", 62500, 12500)}
+# TILE_CASES: case -> (form, L, L2), the tile's kernel form ("run_time": k_fft_tile2_decim_rt, "instantiated":
+# k_fft_tile2_decim) and its two transform lengths; tests/test_length_cases.py holds every row of CASES to the routing
+# restated in tests/decim_cases.py (route()), whose own table takes the tile to every long length.
+TILE_CASES = {("WBFM", 62500, 12500): ("run_time", 250, 50)}
+
+
+def tile_of(kind, B, A):
+    """(form, L, L2) where the decimating tile serves the case, else None."""
+    return TILE_CASES.get((kind, B, A))
 
 
 def resample_site(kind, B, A):
-    if (kind, B, A) in TILE_CASES:
+    if tile_of(kind, B, A) is not None:
         return "decim_tile"
     return "ifft_load" if kind == "WBFM" and CASES[(kind, B, A)][1] == "engine" else "resample_kernel"
 
@@ -354,8 +362,11 @@ def mutant_distances(kind, B, A):
     return out
 
 
-def bound(kind, B, A):
+def bound(kind, B, A, only=None):
     """min(TOL, smallest mutant distance / 10).  That every mutant lies 10 x bound away then holds by construction; what
-    can fail is the other side: the float32 restatement and the oracle within bound / 10 (test_length_cases.py)."""
-    d = [v for per_signal in mutant_distances(kind, B, A).values() for v in per_signal]
+    can fail is the other side: the float32 restatement and the oracle within bound / 10 (test_length_cases.py).
+    `only`: the one mutant that counts (tests/decim_cases.py: "n/2 not doubled", the rule the decimating tile restates;
+    the same-size step of WBFM is another kernel's), default all."""
+    d = [v for name, per_signal in mutant_distances(kind, B, A).items() if only in (None, name) for v in per_signal]
+    assert d or only is None, (kind, B, A, only)
     return min([TOL] + [v / 10.0 for v in d])

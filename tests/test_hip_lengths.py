@@ -12,7 +12,9 @@ one pilot_stage per chunk.  Which restatement of the resampling rule ran is read
 length_cases.resample_site: the decimating tile (no audio_spectrum stage; for WBFM no ifft_A stage), a resampling
 kernel (the audio_spectrum stage: FM / MFM / AM, and WBFM on rocFFT) or, for WBFM on the engine, the load of IFFT_A's
 first pass -- run_wbfm_engine has no audio_spectrum stage at all, its ifft_A stage is the mark; where no decimating
-tile can apply (A >= B, odd A, rocFFT) the tile must not have run.  The pilot kernel form comes from B and from the
+tile can apply (A >= B, odd A, rocFFT) the tile must not have run.  The one rule behind the site is
+length_cases.tile_of -- the tile's form and its two lengths (L, L2), which tests/test_length_cases.py holds to the routing
+restated in tests/decim_cases.py; tests/test_hip_decim_lengths.py takes the tile to every other long length.  The pilot kernel form comes from B and from the
 EFFECTIVE RCFM_OPT_PILOT_BLOCKED the handle reports: tile-blocked, k_pilot_stage_h40 owns whole rows and its branch "the
 channel ends inside this thread's run" is never taken, so a case labelled "h40_ragged" must report 0.
 test_every_cell_of_the_table_was_reached holds the collected (branch, route, pilot kernel) set against the table: a
@@ -139,8 +141,9 @@ def test_batched_call(rc, kind, B, A):
     bound = lc.bound(kind, B, A)
     e_truth, e_ref, ran, planned, blocked = _run_case(rc, case)
     route = _route_of(case)
-    print("%s %d -> %d: %s, %s, engine plans (B, A) %s, pilot blocked %d, vs truth %.2e (bound %.2e), vs oracle %.2e, stages %s"
-          % (kind, B, A, route, lc.resample_site(kind, B, A), planned, blocked, max(e_truth), bound, max(e_ref), ran))
+    print("%s %d -> %d: %s, %s %s, engine plans (B, A) %s, pilot blocked %d, vs truth %.2e (bound %.2e), vs oracle %.2e, stages %s"
+          % (kind, B, A, route, lc.resample_site(kind, B, A), lc.tile_of(kind, B, A) or "", planned, blocked, max(e_truth),
+             bound, max(e_ref), ran))
     assert route == lc.CASES[case], (case, route)
     assert max(e_truth) <= bound, (case, e_truth, bound)
     assert max(e_ref) <= TOL, (case, e_ref)

@@ -14,6 +14,7 @@
 import numpy as np
 import pytest
 
+import decim_cases as dc
 import fft_model
 import length_cases as lc
 import radiocore_oracle as oracle
@@ -21,6 +22,9 @@ import signal_edges as se
 
 STARTUP = 50        # samples of the first buffer that the de-emphasis' initial state reaches (51 taps)
 IDS = ["%s-%d-%d" % c for c in lc.CASES]
+# the conditioning test runs over the decimating tile's own table as well (tests/decim_cases.py: same stations, truth,
+# mutant and bound; no row in both)
+CONDITIONED = list(lc.CASES) + list(dc.CASES)
 
 
 def library_route(B, A):
@@ -36,6 +40,11 @@ def test_table_is_what_the_library_and_the_rules_say():
         site = lc.resample_site(kind, B, A)
         if route == "rocfft" or A >= B or A % 2:             # no decimating tile can apply (fused_fft_decim_ifft_applies)
             assert site == ("ifft_load" if kind == "WBFM" and route == "engine" else "resample_kernel"), (kind, B, A)
+        if kind != "AM":
+            # the routing restated (decim_cases.route): the tile, its form and its two lengths are what the plans give
+            r = dc.route(kind, B, A)
+            took = (r.form, r.L, r.L2) if r is not None and r.form else None
+            assert lc.tile_of(kind, B, A) == took, (kind, B, A, r, "the planner moved this length: exchange it")
         if kind == "WBFM":
             assert B > 2 * 19050, (B, "the pilot band-pass needs 19 050 Hz below B / 2")
             # k_pilot_stage_h40's ragged-end branch exists in its natural-order form only: a case labelled for it must
@@ -47,7 +56,7 @@ def test_table_is_what_the_library_and_the_rules_say():
                 assert not layout, (B, "the planner gives B a tile-blocked layout now: the ragged end would run nowhere")
             if pilot == "h40_blocked":
                 assert layout, (B, "no tile-blocked layout for this plan")
-    assert lc.TILE_CASES <= set(lc.CASES)
+    assert set(lc.TILE_CASES) <= set(lc.CASES) and not set(lc.CASES) & set(dc.CASES)
 
 
 def test_table_covers_every_branch_route_and_pilot_kernel():
@@ -93,9 +102,10 @@ def test_wbfm_chain_with_written_out_steps_is_signal_edges_truth():
     np.testing.assert_array_equal(parts.run(x), plain.run(x))
 
 
-@pytest.mark.parametrize("kind,B,A", list(lc.CASES), ids=IDS)
+@pytest.mark.parametrize("kind,B,A", CONDITIONED, ids=["%s-%d-%d" % c for c in CONDITIONED])
 def test_case_is_well_conditioned_and_tells_the_mutants_apart(kind, B, A):
-    bound = lc.bound(kind, B, A)
+    only = dc.MUTANT if (kind, B, A) in dc.CASES else None          # (decim_cases.bound: the tile's own rule alone)
+    bound = lc.bound(kind, B, A, only)
     assert 0 < bound <= lc.TOL
     want = lc.truths(kind, B, A)
     low = [lc.ref32(kind, B, A) for _ in range(lc.ROWS)]
@@ -115,14 +125,14 @@ def test_case_is_well_conditioned_and_tells_the_mutants_apart(kind, B, A):
                 raw = np.abs(full[r].unclipped)
                 skip = STARTUP if (buf == 0 and kind != "AM") else 0
                 assert np.max(raw[skip:]) < lc.CLIP, (kind, B, A, buf, r, float(np.max(raw[skip:])))
-    dist = lc.mutant_distances(kind, B, A)
+    dist = {k: v for k, v in lc.mutant_distances(kind, B, A).items() if only in (None, k)}
     print("%s %d -> %d: bound %.2e  ref32 %.2e  oracle %.2e  max step %.3f  mutants %s"
           % (kind, B, A, bound, worst32, worst_ref, step, {k: ["%.1e" % v for v in vs] for k, vs in dist.items()}))
     assert worst32 <= bound / 10 and worst_ref <= bound / 10, (worst32, worst_ref, bound)
     assert step <= lc.STEP_CAP, step
     if "even" in lc.branch(B, A):
         assert any(k.startswith("n/2") for k in dist), dist
-    if kind == "WBFM":
+    if kind == "WBFM" and only is None:
         assert "same-size step without its wrap" in dist
     # (bound = min(TOL, smallest distance / 10): this holds by construction and only guards bound()'s own arithmetic; the
     #  checks that can fail are the two above -- the reference within bound / 10, and the mutants being there at all)
