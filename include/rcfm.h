@@ -60,7 +60,8 @@ extern "C" {
                             rcfm_blanker_* added, rcfm_blanker_last in rcfm_tools.h, RCFM_IQ_CF32 = 0 named (new symbols only,
                             nothing existing changed: the load entry points refuse format 0 as before);
                             rcfm_rank_filter and rcfm_floor_* added (new symbols only, nothing existing changed);
-                            rcfm_mix_* added (new symbols only, nothing existing changed) */
+                            rcfm_mix_* added (new symbols only, nothing existing changed);
+                            rcfm_busdyn_* added, rcfm_busdyn_state in rcfm_tools.h (new symbols only, nothing existing changed) */
 
 typedef enum rcfm_status {
     RCFM_OK = 0,
@@ -101,6 +102,7 @@ typedef struct rcfm_audio_filter_s* rcfm_audio_filter_t;
 typedef struct rcfm_gate_s* rcfm_gate_t;
 typedef struct rcfm_floor_s* rcfm_floor_t;
 typedef struct rcfm_mix_s* rcfm_mix_t;
+typedef struct rcfm_busdyn_s* rcfm_busdyn_t;
 typedef struct rcfm_resampler_s* rcfm_resampler_t;
 typedef struct rcfm_feeder_s* rcfm_feeder_t;
 typedef struct rcfm_comm_s* rcfm_comm_t;
@@ -771,6 +773,65 @@ int rcfm_mix_create(int M, const int32_t* bus_start_host, const int32_t* route_c
 int rcfm_mix_run(rcfm_mix_t h, int first, int count, int A, int ch_in, const void* audio, const void* open, void* out,
                  void* active, void* bus_open, void* stream);
 int rcfm_mix_destroy(rcfm_mix_t h);
+
+/* ---- bus dynamics: a look-ahead peak limiter and ducking behind the mixer (no reference counterpart) -----------------------
+ * The mixer's sum has unit gain: four stations at once leave +-1, and rcfm_audio_pack then clamps, which is hard clipping.
+ * This stage knows a peak one block before it arrives and turns the bus down ahead of it, and a side-chain turns one bus
+ * down while another one is active ("the tower bus ducks everything else").  It delays every bus by L samples.
+ *
+ * All arithmetic is float32 and every (+) (-) (x) (/) is one IEEE operation, round to nearest: nothing is contracted to an
+ * fma, the division is the correctly rounded one.  Every maximum is "v > p ? v : p" from p = +0, so a NaN never wins;
+ * min(a, b) is "b < a ? b : a".
+ *
+ * A handle has M buses (1 .. 1024) of ch legs (1 or 2); L (8 .. 2048), the block length in samples, which is both the
+ * look-ahead and the latency; c, the ceiling, finite and > 0; k in (0, 1], the release coefficient per block; and, optional,
+ * per bus m: key[m], -1 or the bus 0 .. M - 1, != m, that ducks bus m; d[m] in (0, 1], the duck depth; thr[m] >= 0, the level
+ * of the key bus above which it counts as active; hold[m], 0 .. 2^15, the blocks of hang after the key bus has fallen silent.
+ * State per bus: tail [L][ch] float32 (zeros after create and reset), h float32 (1.0), hang int32 (0).
+ *
+ * run    in [M][A][ch] float32 (the mixer's out), bus_open_in [M] uint8 or NULL (every bus open); writes out [M][A][ch] and
+ *        bus_open_out [M] uint8 (may be NULL).  Per bus m:
+ *   1. ext[n], n in [-L, A): the tail followed by the row.
+ *   2. a[n] = the maximum over the legs of |ext[n]|.
+ *   3. B = ceil(A / L) blocks with the edges e_j = min(j L, A).
+ *   4. Pk[-1] = the maximum of a over the tail, Pk[j] = the maximum of a over [e_j, e_(j+1)).
+ *   5. Knots: h[0] is the state; for b = 1 .. B in order
+ *        Q = max(Pk[b-2], Pk[b-1]);  T = Q > c ? c (/) Q : 1;
+ *        if key[m] >= 0, with Qk the same maximum over the KEY bus's Pk (its input, never its output: no bus waits for
+ *        another bus's result):  Qk > thr[m]: hang = hold[m], ducking is on;  else hang > 0: hang -= 1, ducking is on;
+ *        else ducking is off.  While ducking is on, T = min(T, d[m]);
+ *        r = h[b-1] (+) ((1 (-) h[b-1]) (x) k);  h[b] = min(T, r).
+ *   6. Output: for n in block j, i = n - j L, len = e_(j+1) - e_j:  w = float32(i + 1) (/) float32(len);
+ *        g = h[j] (+) ((h[j+1] (-) h[j]) (x) w);  y = ext[n - L][leg] (x) g;  out[n][leg] = y > c ? c : (y < -c ? -c : y).
+ *      The clamp is part of the definition: without it the product can exceed c by one ulp.
+ *   7. New state: tail = ext[A - L .. A), h = h[B], hang as step 5 left it.
+ *   8. bus_open_out[m] = bus_open_in[m] != 0 || Pk[-1] > 0: a bus whose channels have just closed still owes L samples.
+ *   9. Every bus runs in every call and its state advances whether or not it is open; an idle bus is a row of +0.
+ * Consequences: |out| <= c for every finite input (an infinite or NaN sample comes out as NaN); a row that never exceeds c, with no duck active, comes out as the input delayed by L bit
+ * for bit (h = T = r = g = 1 exactly); one call of 2 A equals two calls of A when L divides A; A < L works.
+ * Three launches (block peaks, knots -- walked in order, one wave per bus: the recurrence cannot be re-associated -- and apply),
+ * asynchronous on `stream`, no atomics, no device allocation, no host synchronisation; the output bits do not depend on the
+ * 4- or 16-byte alignment of in and out.
+ *
+ * create     A_max: the longest row a run may bring (the scratch for Pk and h is sized from it), 1 .. 2^30.  key_host,
+ *            depth_host, thr_host, hold_host: [M] each, or key_host NULL: no ducking, and the other three are not read.  A
+ *            key chain (a ducks b, b ducks c) is allowed.  RCFM_ERR_ARG before any device call: `out` NULL, M, ch, L, A_max,
+ *            ceiling or release_k outside the ranges above (NaN included), a key table without one of the other three, a
+ *            key outside -1 .. M - 1 or equal to its own bus, a depth, threshold or hold outside its range.
+ * run        RCFM_ERR_ARG before any device call: a NULL handle, in or out, A < 1, A > A_max, in or out not aligned for a
+ *            float, out overlapping in.
+ * reset      every state back to its value after create, on `stream`.
+ * set_fence  as rcfm_gate_set_fence: when on, a run waits for the event the previous run of this handle recorded and
+ *            records its own.  Off by default, and then no event is touched.
+ * destroy    NULL is accepted.
+ * rcfm_tools.h has rcfm_busdyn_state, which copies the state to the host for tests. */
+int rcfm_busdyn_create(int M, int ch, int L, int A_max, float ceiling, float release_k, const int32_t* key_host,
+                       const float* depth_host, const float* thr_host, const int32_t* hold_host, rcfm_busdyn_t* out);
+int rcfm_busdyn_run(rcfm_busdyn_t h, int A, const void* in, const void* bus_open_in, void* out, void* bus_open_out,
+                    void* stream);
+int rcfm_busdyn_reset(rcfm_busdyn_t h, void* stream);
+int rcfm_busdyn_set_fence(rcfm_busdyn_t h, int on);
+int rcfm_busdyn_destroy(rcfm_busdyn_t h);
 
 /* ---- noise blanker: impulse noise removed from the wideband buffer, ahead of the FFT (no reference counterpart) -----------
  * A pulse of a few samples (ignition, switching supplies, electric fences) is white across the band: after rcfm_tuner_load it

@@ -148,6 +148,13 @@ int rcfm_subcarrier_describe(int D, int T, int* J, int* rpad, int* Q, int64_t* l
  * and after a run of n = 0.  What the tests compare with the model (tests/blanker_model.py). */
 int rcfm_blanker_last(rcfm_blanker_t b, void** t_dev, void** hit_words_dev, int64_t* nb);
 
+/* ---- bus dynamics: the state ------------------------------------------------------------------------------------- */
+
+/* The state of a bus dynamics handle (rcfm.h, "bus dynamics") copied to the host: tail_host float32 [M][L][ch], hval_host
+ * float32 [M], hang_host int32 [M]; any of the three may be NULL.  Waits for the whole device first.  What the tests compare
+ * with the model (tests/busdyn_model.py). */
+int rcfm_busdyn_state(rcfm_busdyn_t h, float* tail_host, float* hval_host, int32_t* hang_host);
+
 /* ---- measurement ------------------------------------------------------------ */
 
 /* Per-stage timing with HIP events recorded on the stage's own stream (the reference

@@ -40,6 +40,7 @@ RCFM_SOS_MAX_SECTIONS, RCFM_SOS_RUN, RCFM_SOS_SEGMENT = 8, 33, 8192    # section
 RCFM_GATE_WAVE_FLOATS, RCFM_GATE_SEG_FLOATS, RCFM_GATE_MAX_FRAMES, RCFM_GATE_MAX_RAMP = 4096, 16384, 65535, 1 << 20    # floats of a frame one wave takes; per workgroup of a longer one; F and R of a gate (csrc/gate.h)
 RCFM_FLOOR_MAX_HALF, RCFM_FLOOR_MAX_CELLS = 4096, 1 << 30          # half and M of a rank filter (csrc/floor.h)
 RCFM_MIX_MAX_BUSES, RCFM_MIX_MAX_BUS_ROUTES, RCFM_MIX_MAX_ROUTES, RCFM_MIX_SEGMENT = 1024, 65535, 1 << 20, 16   # M, routes per bus and in all, routes per segment sum (csrc/mix.h)
+RCFM_BUSDYN_MAX_BUSES, RCFM_BUSDYN_MIN_BLOCK, RCFM_BUSDYN_MAX_BLOCK, RCFM_BUSDYN_MAX_HOLD = 1024, 8, 2048, 1 << 15   # M, L and hold of a bus dynamics handle (csrc/busdyn.h)
 RCFM_TUNER_OPT_NARROW_TILES,RCFM_TUNER_OPT_ALIGNED_PLAN = 1, 2                                                                                              # rcfm_tuner_set_option
 
 _ERR_SIZE, _ERR_INDEX, _ERR_RUNTIME, _ERR_ARG, _ERR_STATE = -1, -2, -3, -4, -5
@@ -153,6 +154,13 @@ SIGNATURES = {
     "rcfm_mix_create": [_i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _fp, _i, ctypes.POINTER(_vp)],
     "rcfm_mix_run": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "rcfm_mix_destroy": [_vp],
+    "rcfm_busdyn_create": [_i, _i, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_int32), _fp, _fp,
+                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_vp)],
+    "rcfm_busdyn_run": [_vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "rcfm_busdyn_reset": [_vp, _vp],
+    "rcfm_busdyn_set_fence": [_vp, _i],
+    "rcfm_busdyn_state": [_vp, _fp, _fp, ctypes.POINTER(ctypes.c_int32)],
+    "rcfm_busdyn_destroy": [_vp],
     "rcfm_blanker_create": [_i64, _i, _i, _i, _dbl, _i, _fp, _i, ctypes.POINTER(_vp)],
     "rcfm_blanker_run": [_vp, _i, _i64, _vp, _vp, _vp, _vp],
     "rcfm_blanker_destroy": [_vp],

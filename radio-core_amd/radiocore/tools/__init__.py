@@ -20,4 +20,5 @@ from radiocore.tools.blanker import *
 from radiocore.tools.gate import *
 from radiocore.tools.floor import *
 from radiocore.tools.mix import *
+from radiocore.tools.busdyn import *
 from radiocore.tools import iq, rds, tones, audiofilter

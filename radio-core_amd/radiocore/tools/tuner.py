@@ -13,7 +13,7 @@ from typing import List
 import numpy as np
 
 from radiocore._internal import Injector, hip
-from radiocore.tools import iq, spectrum
+from radiocore.tools import busdyn, iq, spectrum
 from radiocore.tools.floor import OverFloor, channel_noise_gain
 
 __all__ = ["Tuner", "Channel"]
@@ -26,8 +26,10 @@ _DEFAULT_OPTIONS = (True, True, True, 1, True)                         # set_ker
 # What one run_all / run_each queued, on the device, one entry per launch group: blocks [(n, ch, audio [n, A, ch])]; masks, the
 # squelch's uint8 [n], or None (no squelch was set, or nothing was gated); tones, the bank's (P, E), or None (no bank was set);
 # frames, the frame gate's uint8 [n, F + 1], or None (no gate was set).  mix, not per group: None (no mixer was set) or
-# (owner [M], the group each bus belongs to, [(out [M, A, ch_out], active int32 [M], bus_open uint8 [M]) per group]).
-_Run = namedtuple("_Run", "blocks masks tones frames mix", defaults=(None, None, None, None, None))
+# (owner [M], the group each bus belongs to, [(out [M, A, ch_out], active int32 [M], bus_open uint8 [M]) per group]).  dry: None
+# (no bus dynamics were set) or what the mixer itself wrote, in the form of mix -- whose rows and bus_open then are the
+# processed ones -- with the block length L as a fourth entry per group.
+_Run = namedtuple("_Run", "blocks masks tones frames mix dry", defaults=(None, None, None, None, None, None))
 _FRAME_SCRATCH_BYTES = 256 << 20                                       # frame_levels: the most channel IQ held at a time
 
 
@@ -110,6 +112,7 @@ class Tuner(Injector):
         self._gate = None          # set_gate: None (off) or (FrameGate, open float32, close float32: 0-d or [len(channels())]; or two OverFloor)
         self._floor = None         # set_floor: None (off) or the NoiseFloor
         self._mix = None           # set_mix: None (off) or the Mixer
+        self._busdyn = None        # set_bus_dynamics: None (off) or (Limiter, {bus: Duck} or None)
         # What is made FROM a setting -- device copies, "fits this launch plan", what the device handle was last told -- is
         # looked up with what it is made from (_derived) and made again when that differs: nothing invalidates it by hand.
         self._built = {}           # name -> (setting, channel-list version / launch-plan key / handle key, what was made)
@@ -120,6 +123,7 @@ class Tuner(Injector):
         self._floor_handles = {}   # buffer length n -> (NoiseFloor, librcfm handle): the tracked floor, shared by a lane
         self._floor_out = None     # the last load with a floor set: (n, cells, power, floor, {db: thresholds [C]}) on the device, each lane's own
         self._mix_handles = {}     # the launch groups ((first, count), ..) -> (Mixer, channel-list version, owner [M], librcfm handle per group): no state, shared by a lane
+        self._busdyn_handles = {}  # (M, ch_out, the groups' audio lengths) -> ((Limiter, ducks), [(L, librcfm handle) per group]): the limiter's state, shared by a lane
         self._frame_scratch = None # frame_levels: the channel IQ of a chunk, this device tuner's own (allocated by the first call, kept)
         self._blank_handles = {}   # buffer length n -> (the NoiseBlanker it was made by, librcfm handle): this device tuner's own scratch
         self._blank_scratch = None # the blanked copy of a caller's device tensor (buffer's dtype and size; allocated by the first such load)
@@ -168,6 +172,7 @@ class Tuner(Injector):
         self._floor_handles.clear()        # the tracked floor goes with the band
         self._floor_out = None
         self._mix_handles.clear()          # the mixer's tables name channels of the list that goes
+        self._busdyn_handles.clear()       # ... and the buses' tails held their audio
         self._recalculate()
 
     def _recalculate(self, added=None):
@@ -1141,10 +1146,15 @@ class Tuner(Injector):
             if self._bounds and mixer.highest_channel() >= len(self._bounds):
                 raise ValueError("set_mix: a route names channel %d, the tuner has %d channels"
                                  % (mixer.highest_channel(), len(self._bounds)))
+            if self._busdyn is not None and self._busdyn[1] is not None:
+                busdyn.resolve_ducks(self._busdyn[1], mixer.buses)     # the ducks in force must name buses of the new mixer
         if mixer is not self._mix:
             self._mix_handles.clear()              # another mixer: other tables
+            self._busdyn_handles.clear()           # ... and other buses: their dynamics start at rest
+        if mixer is None:
+            self._busdyn = None                    # the dynamics go with the buses (set_bus_dynamics needs a mixer)
         self._mix = mixer
-        self._last = self._last._replace(mix=None)
+        self._last = self._last._replace(mix=None, dry=None)
 
     def _mix_whole(self, what):
         if self._shard is not None or getattr(self, "_slot", None) is not None:
@@ -1176,13 +1186,15 @@ class Tuner(Injector):
                                          hip.ptr(out), hip.ptr(active), hip.ptr(bus_open), hip.stream()))
         return out, active, bus_open
 
-    def mix(self, numpy_output: bool = True):
+    def mix(self, numpy_output: bool = True, dry: bool = False):
         """The buses of this tuner's last ``run_all`` / ``run_each`` / ``run_all_packed`` with a mixer set, float32
         [M, A, ch_out].  After a ``run_each`` over several groups: a list with one [A, ch_out] array per bus (the groups'
-        audio lengths may differ; a bus without a route has the first group's)."""
+        audio lengths may differ; a bus without a route has the first group's).  With ``set_bus_dynamics`` these are the
+        processed rows, ``bus_delay()`` samples late; ``dry=True`` returns the mixer's own rows."""
         if self._last.mix is None:
             raise RuntimeError("mix: no run_all / run_each with a mixer set (set_mix) yet")
-        return self._mix_result(self._last.mix, self._cuda and not numpy_output)
+        which = self._last.dry if dry and self._last.dry is not None else self._last.mix
+        return self._mix_result(which, self._cuda and not numpy_output)
 
     def _mix_result(self, mix, device_output):
         owner, groups = mix
@@ -1202,6 +1214,93 @@ class Tuner(Injector):
         owner, groups = mix
         active = [np.asarray(hip.to_host(g[1])) for g in groups]
         return np.array([active[k][m] for m, k in enumerate(owner)], dtype=np.int32)
+
+    # ---- bus dynamics (rcfm_busdyn_run behind rcfm_mix_run of a group; no reference counterpart) ------------------------
+
+    def set_bus_dynamics(self, limiter=None, ducks=None):
+        """A look-ahead peak limiter, and ducking, on the buses of ``set_mix``: with a ``radiocore.Limiter``, ``run_all`` /
+        ``run_each`` / ``run_all_packed`` (and ``Lanes.submit``) queue rcfm_busdyn_run right behind the mixer of each group,
+        on the caller's stream and without a host synchronisation (include/rcfm.h, "bus dynamics").  No sample of ``mix()``
+        then exceeds the limiter's ceiling, every bus comes ``bus_delay()`` samples late, and ``mix(dry=True)`` still returns
+        the mixer's own rows; ``run_all_packed(buses=True)`` packs the processed rows, and a bus that has gone idle stays
+        open for one more buffer while its tail drains.  ``ducks``: ``{bus index or name: radiocore.Duck}`` -- that bus is
+        turned down while the duck's key bus is active; the key must lie in the same launch group of ``run_each``.  The state
+        (tail, gain, hang) is one per bus, carried from buffer to buffer, kept while the groups' audio lengths stay the same,
+        zeroed by ``reset_states()`` and dropped by ``reset()``, by another mixer and by new settings here.  Limiter and
+        ducks are discretised at each group's audio rate.  No arguments: off, nothing more is launched than before.
+        ValueError -- the setting in force stays -- without a mixer, for ducks without a limiter, for anything but a Limiter
+        and Ducks, for a bus or key the mixer does not have, on a sharded tuner or with a spectrum or window attached."""
+        if limiter is None:
+            if ducks:
+                raise ValueError("set_bus_dynamics: ducks need a limiter (its look-ahead and release shape them)")
+            setting = None
+        else:
+            if not isinstance(limiter, busdyn.Limiter):
+                raise ValueError("set_bus_dynamics takes a radiocore.Limiter")
+            if self._mix is None:
+                raise ValueError("set_bus_dynamics needs a mixer first (set_mix)")
+            try:
+                self._mix_whole("set_bus_dynamics")
+            except RuntimeError as e:
+                raise ValueError(str(e))
+            ducks = dict(ducks) if ducks else None
+            if ducks is not None:
+                busdyn.resolve_ducks(ducks, self._mix.buses)
+            setting = (limiter, ducks)
+        self._busdyn_handles.clear()               # new settings: the dynamics start at rest
+        self._busdyn = setting
+        self._last = self._last._replace(dry=None)
+
+    def _fit_busdyn(self, owner, groups):
+        """[(L, librcfm handle)] per launch group for the bus dynamics in force, made before a run has launched anything:
+        a duck across two groups raises here.  One handle per group, every bus in each (a bus of another group is a row of
+        +0 there); kept while the mixer's shape and the groups' audio lengths stay what they are."""
+        limiter, ducks = self._busdyn
+        M, ch_out = self._mix.M, self._mix.ch_out
+        key = per_bus = None
+        if ducks is not None:
+            key, per_bus = busdyn.resolve_ducks(ducks, self._mix.buses)
+            for m in range(M):
+                if key[m] >= 0 and owner[m] != owner[key[m]]:
+                    raise ValueError("bus %d is ducked by bus %d of another launch group (class, geometry or bandwidth "
+                                     "differ): a duck and its key lie in one group" % (m, key[m]))
+        lengths = tuple(int(g[4]) for g in groups)
+        name = (M, ch_out, lengths)
+        ent = self._busdyn_handles.get(name)
+        if ent is None or ent[0] is not self._busdyn:
+            made = []
+            for A in lengths:
+                L, c, k = limiter.discretise(A)
+                tables = ()
+                if key is not None:
+                    per = [d.discretise(A, L) if d is not None else (np.float32(1.0), np.float32(0.0), 0) for d in per_bus]
+                    tables = (key, [p[0] for p in per], [p[1] for p in per], [p[2] for p in per])
+                h = busdyn.create(M, ch_out, L, A, c, k, *tables)
+                if self._state_fence:
+                    hip.check(self._lib.rcfm_busdyn_set_fence(h.value, 1))
+                made.append((L, h))
+            self._busdyn_handles.clear()           # one shape at a time
+            ent = self._busdyn_handles[name] = (self._busdyn, made)
+        return [(L, h.value) for L, h in ent[1]]
+
+    def _busdyn_group(self, L, h, mixed):
+        # behind the group's rcfm_mix_run on the same stream: (processed rows, the mixer's active, bus_open_out)
+        out, active, bus_open = mixed
+        t = self._torch
+        wet = hip.empty(tuple(out.shape), t.float32)
+        open_out = hip.empty((int(out.shape[0]),), t.uint8)
+        hip.check(self._lib.rcfm_busdyn_run(h, int(out.shape[1]), hip.ptr(out), hip.ptr(bus_open), hip.ptr(wet), hip.ptr(open_out),
+                                            hip.stream()))
+        return wet, active, open_out
+
+    def bus_delay(self):
+        """The delay of the buses in samples, one figure per launch group of this tuner's last run: the limiter's block
+        length L at that group's audio rate, 0 without bus dynamics."""
+        if self._last.mix is None:
+            raise RuntimeError("bus_delay: no run_all / run_each with a mixer set (set_mix) yet")
+        if self._last.dry is None:
+            return [0] * len(self._last.mix[1])
+        return [g[3] for g in self._last.dry[1]]
 
     def _gates(self, handle, first, count, audio):
         """What follows a group's rcfm_pipeline_run on the same stream: the tone bank, the audio filter, the level squelch
@@ -1294,9 +1393,10 @@ class Tuner(Injector):
         self._fit_afilt(self._afilt)
         self._fit_gate(self._gate)
         owner, mixes = self._fit_mix(tuple((g[0], g[1]) for g in groups)) if self._mix is not None else (None, None)
+        dynamics = self._fit_busdyn(owner, groups) if mixes is not None and self._busdyn is not None else None
         gated = self._squelch is not None or self._gate is not None or (self._tones is not None and self._tones[1] is not None)
         run = _Run([], [] if gated else None, [] if self._tones is not None else None, [] if self._gate is not None else None,
-                   (owner, []) if mixes is not None else None)
+                   (owner, []) if mixes is not None else None, (owner, []) if dynamics is not None else None)
         for k, (first, count, kind, B, A, tau, *agc) in enumerate(groups):
             ch = 2 if kind == hip.RCFM_WBFM else 1
             audio = hip.empty((count, A, ch), self._torch.float32)
@@ -1314,8 +1414,12 @@ class Tuner(Injector):
             if run.frames is not None:
                 run.frames.append(frames)
             if run.mix is not None:
-                run.mix[1].append(self._mix_group(mixes[k], first, count, audio, mask))
-        self._last = _Run(None, run.masks, run.tones, run.frames, run.mix)
+                mixed = self._mix_group(mixes[k], first, count, audio, mask)
+                if run.dry is not None:
+                    run.dry[1].append(mixed + (dynamics[k][0],))
+                    mixed = self._busdyn_group(*dynamics[k], mixed)
+                run.mix[1].append(mixed)
+        self._last = _Run(None, run.masks, run.tones, run.frames, run.mix, run.dry)
         return run
 
     def run_all_packed(self, pcm, numpy_output: bool = True, chunk: int = 0, drain=None, buses: bool = False):
@@ -1429,6 +1533,9 @@ class Tuner(Injector):
             hip.check(self._lib.rcfm_gate_reset(h.value, hip.stream()))
         for _, h in self._floor_handles.values():
             hip.check(self._lib.rcfm_floor_reset(h.value, hip.stream()))
+        for _, made in self._busdyn_handles.values():
+            for _, h in made:
+                hip.check(self._lib.rcfm_busdyn_reset(h.value, hip.stream()))
 
     def set_kernel_options(self, lds_chain=True, fused_tiles=True, phase_link=True, narrow_tiles=1, ssb_direct=True):
         """Which forms of the kernel chain run_all / run_each may use (rcfm_demod_set_option; no reference
@@ -1514,6 +1621,9 @@ class Tuner(Injector):
             hip.check(self._lib.rcfm_gate_set_fence(h.value, 1))
         for _, h in self._floor_handles.values():
             hip.check(self._lib.rcfm_floor_set_fence(h.value, 1))
+        for _, made in self._busdyn_handles.values():
+            for _, h in made:
+                hip.check(self._lib.rcfm_busdyn_set_fence(h.value, 1))
 
     def _lane_clone(self):
         """A second Tuner over the SAME channel list, demodulator objects and de-emphasis state, with its own device
@@ -1526,7 +1636,8 @@ class Tuner(Injector):
         t._afilt_handles = self._afilt_handles    # ... and one audio filter state ...
         t._gate_handles = self._gate_handles      # ... and one frame gate state ...
         t._floor_handles = self._floor_handles    # ... and one tracked noise floor ...
-        t._mix_handles = self._mix_handles        # ... and the mixer's tables, which hold no state; every other device handle is the lane's own
+        t._mix_handles = self._mix_handles        # ... and the mixer's tables, which hold no state ...
+        t._busdyn_handles = self._busdyn_handles  # ... and one state of the bus dynamics; every other device handle is the lane's own
         t._sync_lane(self)
         return t
 
@@ -1534,9 +1645,9 @@ class Tuner(Injector):
         """Follow the base tuner: its settings, each a new object per set_* -- what this lane made from the old one is made
         again when it is next used (_derived), on the lane's own stream -- and its channel list."""
         if self._tones is not base._tones or self._squelch is not base._squelch or self._gate is not base._gate or \
-                self._mix is not base._mix:
+                self._mix is not base._mix or self._busdyn is not base._busdyn:
             self._last = _Run()                            # (Lanes keeps each buffer's results with its ticket)
-        self._mix = base._mix
+        self._mix, self._busdyn = base._mix, base._busdyn
         if self._blanker is not base._blanker:
             self.set_blanker(None)                         # the handle and scratch of this lane's own go with their blanker
         if self._floor is not base._floor:
