@@ -193,13 +193,8 @@ using namespace rcfm;
 struct rcfm_audio_filter_s {
     int C = 0, ch = 0, S = 0;
     DeviceBuffer sections, state;      // SosSection [S]; float64 [C][ch][S][2]
-    // rcfm_audio_filter_set_fence: a run waits for the event the previous run recorded, on whichever stream that was
-    hipEvent_t ev = nullptr;
-    bool armed = false, recorded = false;
+    StreamFence fence;                 // rcfm_audio_filter_set_fence
     size_t state_bytes() const { return (size_t)C * ch * S * 2 * sizeof(double); }
-    ~rcfm_audio_filter_s() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 extern "C" {
@@ -256,7 +251,7 @@ int rcfm_audio_filter_run(rcfm_audio_filter_t f, int first, int count, int n, co
         double* st = f->state.as<double>() + (size_t)first * f->ch * f->S * 2;
         const SosSection* sec = f->sections.as<SosSection>();
         const bool vec = ((int64_t)n * f->ch) % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-        if (f->armed && f->recorded) RC_HIP(hipStreamWaitEvent(s, f->ev, 0));
+        StreamFence::Scope fenced(f->fence, s);
         const dim3 grid((unsigned)count), block(kSosThreads);
         if (f->ch == 1) {
             if (vec)
@@ -270,10 +265,6 @@ int rcfm_audio_filter_run(rcfm_audio_filter_t f, int first, int count, int n, co
                 hipLaunchKernelGGL((k_audio_filter<2, false>), grid, block, 0, s, x, y, n, f->S, sec, st, sel);
         }
         RC_HIP(hipGetLastError());
-        if (f->armed) {
-            RC_HIP(hipEventRecord(f->ev, s));
-            f->recorded = true;
-        }
     });
 }
 
@@ -287,25 +278,21 @@ int rcfm_audio_filter_reset(rcfm_audio_filter_t f, void* stream) {
 int rcfm_audio_filter_get_state(rcfm_audio_filter_t f, double* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(f && state_host, RCFM_ERR_ARG, "NULL argument");
-        RC_HIP(hipMemcpyAsync(state_host, f->state.get(), f->state_bytes(), hipMemcpyDeviceToHost, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_host(state_host, f->state.get(), f->state_bytes(), as_stream(stream));
     });
 }
 
 int rcfm_audio_filter_set_state(rcfm_audio_filter_t f, const double* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(f && state_host, RCFM_ERR_ARG, "NULL argument");
-        RC_HIP(hipMemcpyAsync(f->state.get(), state_host, f->state_bytes(), hipMemcpyHostToDevice, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_device(f->state.get(), state_host, f->state_bytes(), as_stream(stream));
     });
 }
 
 int rcfm_audio_filter_set_fence(rcfm_audio_filter_t f, int on) {
     return guarded([&] {
         RC_REQUIRE(f, RCFM_ERR_ARG, "NULL handle");
-        if (on != 0 && f->ev == nullptr) RC_HIP(hipEventCreateWithFlags(&f->ev, hipEventDisableTiming));
-        f->armed = on != 0;
-        if (!f->armed) f->recorded = false;
+        f->fence.arm(on != 0);
     });
 }
 

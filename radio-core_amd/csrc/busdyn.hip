@@ -207,9 +207,7 @@ struct rcfm_busdyn_s {
     DeviceBuffer epoch;                    // uint32 [1]: the runs so far; the tail is slot epoch & 1
     DeviceBuffer peaks, knots;             // scratch, float32 [M][B + 1] of a run, each sized for B = ceil(A_max / L)
     DeviceBuffer key, depth, thr, hold;
-    // rcfm_busdyn_set_fence: a run waits for the event the previous run recorded, on whichever stream that was
-    hipEvent_t ev = nullptr;
-    bool armed = false, recorded = false;
+    StreamFence fence;                     // rcfm_busdyn_set_fence
     size_t tail_floats() const { return (size_t)M * L * ch; }
     unsigned knot_grid() const { return (unsigned)((M + kBusdynKnotThreads - 1) / kBusdynKnotThreads); }   // of k_busdyn_ones
     void rest(hipStream_t s) {
@@ -218,9 +216,6 @@ struct rcfm_busdyn_s {
         RC_HIP(hipMemsetAsync(epoch.get(), 0, sizeof(uint32_t), s));
         hipLaunchKernelGGL(k_busdyn_ones, dim3(knot_grid()), dim3(kBusdynKnotThreads), 0, s, hval.as<float>(), M);
         RC_HIP(hipGetLastError());
-    }
-    ~rcfm_busdyn_s() {
-        if (ev) (void)hipEventDestroy(ev);
     }
 };
 
@@ -280,7 +275,7 @@ int rcfm_busdyn_run(rcfm_busdyn_t h, int A, const void* in, const void* bus_open
         const size_t bytes = sizeof(float) * (size_t)M * (size_t)A * (size_t)ch;
         RC_REQUIRE(i0 + bytes <= o0 || o0 + bytes <= i0, RCFM_ERR_ARG, "out overlaps in");
         hipStream_t s = as_stream(stream);
-        if (h->armed && h->recorded) RC_HIP(hipStreamWaitEvent(s, h->ev, 0));
+        StreamFence::Scope fenced(h->fence, s);
         const int B = (A + L - 1) / L;
         const int64_t row = (int64_t)A * ch, lag = (int64_t)L * ch;
         const float* x = static_cast<const float*>(in);
@@ -310,10 +305,6 @@ int rcfm_busdyn_run(rcfm_busdyn_t h, int A, const void* in, const void* bus_open
             hipLaunchKernelGGL((k_busdyn_apply<false>), agrid, dim3(kBusdynThreads), 0, s, x, tails, epoch, H, M, A, L, ch, B, nbx,
                                h->c, static_cast<float*>(out));
         RC_HIP(hipGetLastError());
-        if (h->armed) {
-            RC_HIP(hipEventRecord(h->ev, s));
-            h->recorded = true;
-        }
     });
 }
 
@@ -327,9 +318,7 @@ int rcfm_busdyn_reset(rcfm_busdyn_t h, void* stream) {
 int rcfm_busdyn_set_fence(rcfm_busdyn_t h, int on) {
     return guarded([&] {
         RC_REQUIRE(h, RCFM_ERR_ARG, "NULL handle");
-        if (on != 0 && h->ev == nullptr) RC_HIP(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
-        h->armed = on != 0;
-        if (!h->armed) h->recorded = false;
+        h->fence.arm(on != 0);
     });
 }
 

@@ -142,4 +142,55 @@ class DeviceBuffer {
 
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
 
+// The stream fence of a handle whose device state is carried from buffer to buffer (rcfm_*_set_fence,
+// RCFM_OPT_STATE_FENCE): such a handle may run consecutive buffers on DIFFERENT streams (radiocore.tools.Lanes), and
+// every launch sequence that reads or writes the state then waits for the event the previous one recorded, on whichever
+// stream that was.  Disarmed (the default) it touches no event.
+class StreamFence {
+   public:
+    StreamFence() = default;
+    StreamFence(const StreamFence&) = delete;
+    StreamFence& operator=(const StreamFence&) = delete;
+    ~StreamFence() {
+        if (ev_) (void)hipEventDestroy(ev_);
+    }
+    void arm(bool on) {
+        if (on && ev_ == nullptr) RC_HIP(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
+        armed_ = on;
+        if (!armed_) recorded_ = false;
+    }
+    bool armed() const { return armed_; }
+    // Scope of the launches that touch the state on stream s: waits on entry, records on exit -- also when a launch in
+    // between has thrown, and without throwing itself.
+    class Scope {
+       public:
+        Scope(StreamFence& f, hipStream_t s) : f_(f), s_(s) {
+            if (f_.armed_ && f_.recorded_) RC_HIP(hipStreamWaitEvent(s_, f_.ev_, 0));
+        }
+        ~Scope() {
+            if (f_.armed_ && hipEventRecord(f_.ev_, s_) == hipSuccess) f_.recorded_ = true;
+        }
+        Scope(const Scope&) = delete;
+        Scope& operator=(const Scope&) = delete;
+
+       private:
+        StreamFence& f_;
+        hipStream_t s_;
+    };
+
+   private:
+    hipEvent_t ev_ = nullptr;
+    bool armed_ = false, recorded_ = false;
+};
+
+// rcfm_*_get_state / rcfm_*_set_state behind their argument checks: the copy on the caller's stream, and its end awaited.
+inline void state_to_host(void* host, const void* dev, size_t bytes, hipStream_t s) {
+    RC_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+    RC_HIP(hipStreamSynchronize(s));
+}
+inline void state_to_device(void* dev, const void* host, size_t bytes, hipStream_t s) {
+    RC_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s));
+    RC_HIP(hipStreamSynchronize(s));
+}
+
 }  // namespace rcfm

@@ -3,6 +3,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <optional>
 
 #include "agc.h"
 #include "api_internal.h"
@@ -29,26 +30,11 @@ struct rcfm_demod_s {
     // per-channel caller and the batched caller carry ONE state per channel like the reference's
     // Deemphasis._state (deemphasis.py:48-49,64).
     // RCFM_OPT_STATE_FENCE: handles that share one state buffer may run consecutive buffers on DIFFERENT streams (one
-    // handle set per stream, radiocore.tools.Lanes): every launch sequence that reads or writes the state then waits
-    // for the event the previous one recorded.  The fence travels with the buffer (bind_state shares both).
+    // handle set per stream, radiocore.tools.Lanes).  The fence travels with the buffer (bind_state shares both).
     struct StateBuf : DeviceBuffer {
-        hipEvent_t ev = nullptr;
-        bool armed = false, recorded = false;
-        ~StateBuf() {
-            if (ev) (void)hipEventDestroy(ev);
-        }
+        StreamFence fence;
     };
     std::shared_ptr<StateBuf> state_buf = std::make_shared<StateBuf>();
-    struct StateFence {   // scope of the launches that touch the state on stream s
-        StateBuf& b;
-        hipStream_t s;
-        StateFence(rcfm_demod_s& d, hipStream_t st) : b(*d.state_buf), s(st) {
-            if (b.armed && b.recorded) RC_HIP(hipStreamWaitEvent(s, b.ev, 0));
-        }
-        ~StateFence() {
-            if (b.armed && hipEventRecord(b.ev, s) == hipSuccess) b.recorded = true;
-        }
-    };
     size_t state_off = 0;   // floats into state_buf
     float* state_ptr() const { return state_buf->as<float>() + state_off; }
     float* state_at(int first) const { return state_ptr() + (size_t)first * state_stride(); }   // channel `first`'s slot
@@ -123,7 +109,7 @@ struct rcfm_demod_s {
     bool carries_state() const { return stateful() || agc_on; }
     size_t state_stride() const { return stateful() ? (size_t)ch * 50 : 1; }   // floats per channel
     void agc_tail(int first, int cnt, float* audio, hipStream_t s) {
-        StateFence fence(*this, s);
+        StreamFence::Scope fenced(state_buf->fence, s);
         StageTimer tm(kind == RCFM_AM ? ST_AM_TAIL : ST_SSB_TAIL, s);
         launch_agc_tail(kind == RCFM_AM ? RCFM_AGC_CARRIER : RCFM_AGC_PEAK, audio, audio, A, cnt,
                         agc_params(agc_decay, agc_level, agc_floor), state_at(first), s);
@@ -270,7 +256,7 @@ struct rcfm_demod_s {
                         int row = 0, int pitch = 0) {
         float* st = state_at(first);
         const bool fast = !generic_fir && ((int64_t)A * ch) % 4 == 0;
-        StateFence fence(*this, s);
+        StreamFence::Scope fenced(state_buf->fence, s);
         if (fast && A >= 50) {
             // de-emphasis, DC removal and clip in one kernel: the mean comes from the DC bin (buf_dc)
             {
@@ -662,8 +648,8 @@ struct rcfm_demod_s {
             a.dc = nullptr;
         }
         {
-            std::unique_ptr<StateFence> fence;   // the on-chip de-emphasis reads and writes the state
-            if (deemph_on_chip) fence = std::make_unique<StateFence>(*this, s);
+            std::optional<StreamFence::Scope> fenced;   // the on-chip de-emphasis reads and writes the state
+            if (deemph_on_chip) fenced.emplace(state_buf->fence, s);
             StageTimer tm(ST_LDS_CHAIN, s);
             RC_REQUIRE(launch_lds_chain(B, A, a, s), RCFM_ERR_RUNTIME, "LDS chain refused a geometry it lists");
         }
@@ -673,7 +659,7 @@ struct rcfm_demod_s {
     // RCFM_OPT_GRAPH for a one-channel call: replay the graph captured for these pointers, or capture one on the second
     // call in a row with them.  false: the caller launches the chain itself.
     bool run_graphed(int first, const float2* iq, float* audio, hipStream_t s) {
-        if (!opt_graph || !eng_B || g_prof.mask != 0 || state_buf->armed || agc_on) return false;   // AGC: never captured
+        if (!opt_graph || !eng_B || g_prof.mask != 0 || state_buf->fence.armed() || agc_on) return false;   // AGC: never captured
         const float* st = stateful() ? state_ptr() : nullptr;
         for (auto& g : graphs)
             if (g.iq == iq && g.audio == audio && g.first == first && g.state == st) {
@@ -796,9 +782,7 @@ int rcfm_demod_get_state(rcfm_demod_t d, float* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
         if (!d->stateful()) return;
-        RC_HIP(hipMemcpyAsync(state_host, d->state_ptr(), (size_t)d->C * d->ch * 50 * sizeof(float),
-                              hipMemcpyDeviceToHost, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_host(state_host, d->state_ptr(), (size_t)d->C * d->ch * 50 * sizeof(float), as_stream(stream));
     });
 }
 
@@ -806,9 +790,7 @@ int rcfm_demod_set_state(rcfm_demod_t d, const float* state_host, void* stream) 
     return guarded([&] {
         RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
         if (!d->stateful()) return;
-        RC_HIP(hipMemcpyAsync(d->state_ptr(), state_host, (size_t)d->C * d->ch * 50 * sizeof(float),
-                              hipMemcpyHostToDevice, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_device(d->state_ptr(), state_host, (size_t)d->C * d->ch * 50 * sizeof(float), as_stream(stream));
     });
 }
 
@@ -857,13 +839,7 @@ int rcfm_demod_set_option(rcfm_demod_t d, int option, int value) {
                 RC_REQUIRE(value >= 0 && value <= 2, RCFM_ERR_ARG, "narrow tiles: 0 never, 1 automatic, 2 always");
                 d->opt_narrow = value;
                 break;
-            case RCFM_OPT_STATE_FENCE: {
-                auto& b = *d->state_buf;
-                if (value != 0 && b.ev == nullptr) RC_HIP(hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
-                b.armed = value != 0;
-                if (!b.armed) b.recorded = false;
-                break;
-            }
+            case RCFM_OPT_STATE_FENCE: d->state_buf->fence.arm(value != 0); break;
             default: RC_REQUIRE(false, RCFM_ERR_ARG, "unknown demodulator option");
         }
     });
@@ -886,7 +862,7 @@ int rcfm_demod_get_option(rcfm_demod_t d, int option, int* value) {
             case RCFM_OPT_PHASE_LINK: *value = d->opt_phase_link; break;
             case RCFM_OPT_SSB_DIRECT: *value = d->opt_ssb_direct; break;
             case RCFM_OPT_NARROW_TILES: *value = d->opt_narrow; break;
-            case RCFM_OPT_STATE_FENCE: *value = d->state_buf->armed; break;
+            case RCFM_OPT_STATE_FENCE: *value = d->state_buf->fence.armed(); break;
             // 0 = off (or this runtime refused the capture), 1 = on, 1 + k = on and k captured chains are being replayed
             case RCFM_OPT_GRAPH: *value = d->opt_graph ? 1 + (int)d->graphs.size() : 0; break;
             default: RC_REQUIRE(false, RCFM_ERR_ARG, "unknown demodulator option");
@@ -921,9 +897,7 @@ int rcfm_demod_get_agc_state(rcfm_demod_t d, float* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
         RC_REQUIRE(d->agc_on, RCFM_ERR_STATE, "this demodulator has no AGC (rcfm_demod_set_agc)");
-        RC_HIP(hipMemcpyAsync(state_host, d->state_ptr(), (size_t)d->C * sizeof(float), hipMemcpyDeviceToHost,
-                              as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_host(state_host, d->state_ptr(), (size_t)d->C * sizeof(float), as_stream(stream));
     });
 }
 
@@ -931,9 +905,7 @@ int rcfm_demod_set_agc_state(rcfm_demod_t d, const float* state_host, void* stre
     return guarded([&] {
         RC_REQUIRE(d && state_host, RCFM_ERR_ARG, "NULL argument");
         RC_REQUIRE(d->agc_on, RCFM_ERR_STATE, "this demodulator has no AGC (rcfm_demod_set_agc)");
-        RC_HIP(hipMemcpyAsync(d->state_ptr(), state_host, (size_t)d->C * sizeof(float), hipMemcpyHostToDevice,
-                              as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_device(d->state_ptr(), state_host, (size_t)d->C * sizeof(float), as_stream(stream));
     });
 }
 

@@ -145,13 +145,8 @@ struct rcfm_floor_s {
     int half = 0, guard = 0, q = 0;
     float rise = 1.f, fall = 1.f;
     DeviceBuffer state;                // float32 [M]; NaN: not primed
-    // rcfm_floor_set_fence: a run waits for the event the previous run recorded, on whichever stream that was
-    hipEvent_t ev = nullptr;
-    bool armed = false, recorded = false;
+    StreamFence fence;                 // rcfm_floor_set_fence
     size_t state_bytes() const { return (size_t)M * sizeof(float); }
-    ~rcfm_floor_s() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 extern "C" {
@@ -191,13 +186,9 @@ int rcfm_floor_run(rcfm_floor_t h, const void* power, float ratio, void* floor, 
         RC_REQUIRE((uintptr_t)power % 4 == 0 && (uintptr_t)floor % 4 == 0, RCFM_ERR_ARG,
                    "misaligned buffer: power and floor are aligned for a float");
         hipStream_t s = as_stream(stream);
-        if (h->armed && h->recorded) RC_HIP(hipStreamWaitEvent(s, h->ev, 0));
+        StreamFence::Scope fenced(h->fence, s);
         launch_floor(static_cast<const float*>(power), h->M, h->half, h->guard, h->q, h->state.as<float>(), h->rise, h->fall,
                      ratio, static_cast<float*>(floor), static_cast<uint8_t*>(over), s);
-        if (h->armed) {
-            RC_HIP(hipEventRecord(h->ev, s));
-            h->recorded = true;
-        }
     });
 }
 
@@ -226,25 +217,21 @@ int rcfm_floor_reset(rcfm_floor_t h, void* stream) {
 int rcfm_floor_get_state(rcfm_floor_t h, float* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(h && state_host, RCFM_ERR_ARG, "NULL argument");
-        RC_HIP(hipMemcpyAsync(state_host, h->state.get(), h->state_bytes(), hipMemcpyDeviceToHost, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_host(state_host, h->state.get(), h->state_bytes(), as_stream(stream));
     });
 }
 
 int rcfm_floor_set_state(rcfm_floor_t h, const float* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(h && state_host, RCFM_ERR_ARG, "NULL argument");
-        RC_HIP(hipMemcpyAsync(h->state.get(), state_host, h->state_bytes(), hipMemcpyHostToDevice, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_device(h->state.get(), state_host, h->state_bytes(), as_stream(stream));
     });
 }
 
 int rcfm_floor_set_fence(rcfm_floor_t h, int on) {
     return guarded([&] {
         RC_REQUIRE(h, RCFM_ERR_ARG, "NULL handle");
-        if (on != 0 && h->ev == nullptr) RC_HIP(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
-        h->armed = on != 0;
-        if (!h->armed) h->recorded = false;
+        h->fence.arm(on != 0);
     });
 }
 

@@ -254,13 +254,8 @@ using namespace rcfm;
 struct rcfm_gate_s {
     int C = 0, hang = 0, lead = 0, R = 0;
     DeviceBuffer state, ramp;          // int32 [C][2]: open, hang_left; float32 [R]
-    // rcfm_gate_set_fence: a run waits for the event the previous run recorded, on whichever stream that was
-    hipEvent_t ev = nullptr;
-    bool armed = false, recorded = false;
+    StreamFence fence;                 // rcfm_gate_set_fence
     size_t state_bytes() const { return (size_t)C * 2 * sizeof(int32_t); }
-    ~rcfm_gate_s() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 extern "C" {
@@ -334,16 +329,12 @@ int rcfm_gate_run(rcfm_gate_t g, int first, int count, int F, const void* power,
         RC_REQUIRE(first >= 0 && (int64_t)first + count <= g->C, RCFM_ERR_INDEX, "first .. first + count is outside the gate's channels");
         if (count == 0) return;
         hipStream_t s = as_stream(stream);
-        if (g->armed && g->recorded) RC_HIP(hipStreamWaitEvent(s, g->ev, 0));
+        StreamFence::Scope fenced(g->fence, s);
         hipLaunchKernelGGL(k_gate_run, dim3((unsigned)((count + kGateThreads - 1) / kGateThreads)), dim3(kGateThreads), 0, s,
                            g->state.as<int32_t>() + 2 * (size_t)first, static_cast<const float*>(power),
                            static_cast<const float*>(open_thr), static_cast<const float*>(close_thr), count, F, g->hang, g->lead,
                            static_cast<uint8_t*>(frame_mask), static_cast<uint8_t*>(open_any));
         RC_HIP(hipGetLastError());
-        if (g->armed) {
-            RC_HIP(hipEventRecord(g->ev, s));
-            g->recorded = true;
-        }
     });
 }
 
@@ -388,25 +379,21 @@ int rcfm_gate_reset(rcfm_gate_t g, void* stream) {
 int rcfm_gate_get_state(rcfm_gate_t g, int32_t* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(g && state_host, RCFM_ERR_ARG, "NULL argument");
-        RC_HIP(hipMemcpyAsync(state_host, g->state.get(), g->state_bytes(), hipMemcpyDeviceToHost, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_host(state_host, g->state.get(), g->state_bytes(), as_stream(stream));
     });
 }
 
 int rcfm_gate_set_state(rcfm_gate_t g, const int32_t* state_host, void* stream) {
     return guarded([&] {
         RC_REQUIRE(g && state_host, RCFM_ERR_ARG, "NULL argument");
-        RC_HIP(hipMemcpyAsync(g->state.get(), state_host, g->state_bytes(), hipMemcpyHostToDevice, as_stream(stream)));
-        RC_HIP(hipStreamSynchronize(as_stream(stream)));
+        state_to_device(g->state.get(), state_host, g->state_bytes(), as_stream(stream));
     });
 }
 
 int rcfm_gate_set_fence(rcfm_gate_t g, int on) {
     return guarded([&] {
         RC_REQUIRE(g, RCFM_ERR_ARG, "NULL handle");
-        if (on != 0 && g->ev == nullptr) RC_HIP(hipEventCreateWithFlags(&g->ev, hipEventDisableTiming));
-        g->armed = on != 0;
-        if (!g->armed) g->recorded = false;
+        g->fence.arm(on != 0);
     });
 }
 

@@ -46,6 +46,38 @@ class _Part:
         return self._whole[self._first:self._first + self._count]
 
 
+class _Carried(dict):
+    """One cache of librcfm handles whose device state is carried from buffer to buffer and shared with the lanes (DESIGN.md,
+    "carried state"): a dict with the entry layout its stage chose, which knows where the hip.Handles sit in an entry and
+    which ABI functions put such a handle's state back to rest and arm its fence (None: it has none).  The Tuner walks
+    them in one ordered collection (``_carried``) and stores with ``put``, which arms a handle made after the lanes were."""
+
+    def __init__(self, handles_of, reset=None, fence=None):
+        super().__init__()
+        self._handles_of, self._reset, self._fence = handles_of, reset, fence
+
+    def _each(self, name, entries, arg):
+        if name is not None:
+            for h in [h for e in entries for h in self._handles_of(e)]:
+                hip.check(getattr(hip.lib(), name)(h.value, arg))
+
+    def reset_states(self):
+        self._each(self._reset, self.values(), hip.stream())
+
+    def arm(self):
+        self._each(self._fence, self.values(), 1)
+
+    def put(self, key, entry, fenced):
+        self._each(self._fence, (entry,) if fenced else (), 1)
+        self[key] = entry
+        return entry
+
+
+# _sync_lane: the settings a lane follows -> what of the lane's own a new one drops (None: it is made again when next used, _derived)
+_FOLLOWED = {"_squelch": "last", "_tones": "last", "_gate": "last", "_mix": "last", "_busdyn": "last", "_blanker": "blanker",
+             "_floor": "floor", "_afilt": None, "_iq_balance": None, "_fine": None}
+
+
 def _key_agc(key):
     """The AGC setting (decay_samples, level, floor) a _batched key ends with, or None."""
     last = key[-1]
@@ -117,13 +149,17 @@ class Tuner(Injector):
         # looked up with what it is made from (_derived) and made again when that differs: nothing invalidates it by hand.
         self._built = {}           # name -> (setting, channel-list version / launch-plan key / handle key, what was made)
         self._last = _Run()        # masks and tone powers of the last run_all / run_each (not its audio: the caller's)
-        # Device state that is no copy of a setting: the filter's, shared by a lane, and the blanker's, each lane's own.
-        self._afilt_handles = {}   # (legs, A) -> (channels, AudioFilter, librcfm handle): the filter's states, by channel index
-        self._gate_handles = {}    # A -> (channels, FrameGate, librcfm handle): the gate's states, by channel index, shared by a lane
-        self._floor_handles = {}   # buffer length n -> (NoiseFloor, librcfm handle): the tracked floor, shared by a lane
+        # Device state that is no copy of a setting.  What is carried from buffer to buffer: one cache per stage, each also the attribute of
+        # its name, in the order reset_states() and _arm_state_fence() walk; reset() empties them, a lane shares them.  A new stage adds ONE entry.
+        self._carried = {
+            "_afilt_handles": _Carried(lambda e: e[2:], "rcfm_audio_filter_reset", "rcfm_audio_filter_set_fence"),   # (legs, A) -> (channels, AudioFilter, librcfm handle): the filter's states, by channel index
+            "_gate_handles": _Carried(lambda e: e[2:], "rcfm_gate_reset", "rcfm_gate_set_fence"),   # A -> (channels, FrameGate, librcfm handle): the gate's states, by channel index
+            "_floor_handles": _Carried(lambda e: e[1:], "rcfm_floor_reset", "rcfm_floor_set_fence"),   # buffer length n -> (NoiseFloor, librcfm handle): the tracked floor
+            "_mix_handles": _Carried(lambda e: e[3]),   # the launch groups ((first, count), ..) -> (Mixer, channel-list version, owner [M], librcfm handle per group): no state
+            "_busdyn_handles": _Carried(lambda e: [h for _, h in e[1]], "rcfm_busdyn_reset", "rcfm_busdyn_set_fence"),   # (M, ch_out, the groups' audio lengths) -> ((Limiter, ducks), [(L, librcfm handle) per group]): the limiter's state
+        }
+        self.__dict__.update(self._carried)
         self._floor_out = None     # the last load with a floor set: (n, cells, power, floor, {db: thresholds [C]}) on the device, each lane's own
-        self._mix_handles = {}     # the launch groups ((first, count), ..) -> (Mixer, channel-list version, owner [M], librcfm handle per group): no state, shared by a lane
-        self._busdyn_handles = {}  # (M, ch_out, the groups' audio lengths) -> ((Limiter, ducks), [(L, librcfm handle) per group]): the limiter's state, shared by a lane
         self._frame_scratch = None # frame_levels: the channel IQ of a chunk, this device tuner's own (allocated by the first call, kept)
         self._blank_handles = {}   # buffer length n -> (the NoiseBlanker it was made by, librcfm handle): this device tuner's own scratch
         self._blank_scratch = None # the blanked copy of a caller's device tensor (buffer's dtype and size; allocated by the first such load)
@@ -167,12 +203,9 @@ class Tuner(Injector):
         """Forget all channels (raises ValueError like the reference: min() of nothing)."""
         self._bounds = []
         self._lo = self._hi = self._bw_sum = None
-        self._afilt_handles.clear()        # the audio filter's states belong to the channels
-        self._gate_handles.clear()         # ... and so do the frame gate's
-        self._floor_handles.clear()        # the tracked floor goes with the band
+        for cache in self._carried.values():
+            cache.clear()                  # the carried states belong to the channels, the tracked floor to their band
         self._floor_out = None
-        self._mix_handles.clear()          # the mixer's tables name channels of the list that goes
-        self._busdyn_handles.clear()       # ... and the buses' tails held their audio
         self._recalculate()
 
     def _recalculate(self, added=None):
@@ -697,10 +730,7 @@ class Tuner(Injector):
         nf = self._floor
         ent = self._floor_handles.get(n)
         if ent is None or ent[0] is not nf:
-            h = nf._create(nf.cells(n))
-            if self._state_fence:
-                hip.check(self._lib.rcfm_floor_set_fence(h.value, 1))
-            ent = self._floor_handles[n] = (nf, h)
+            ent = self._floor_handles.put(n, (nf, nf._create(nf.cells(n))), self._state_fence)
         return ent[1].value
 
     def _floor_pass(self, handle, n):
@@ -919,25 +949,28 @@ class Tuner(Injector):
                 setting[0].sections(A)
         self._fit("filter fit", setting, check)
 
+    def _channel_states(self, cache, key, owner, create, shape, ctype, get_state, set_state):
+        """The handle cache[key] -> (channels, owner, handle) of a stage with one state of `shape` (of `ctype`) per channel:
+        ``create(C)``, sized for all channels -- the state slots are addressed by channel index, so shard and regrouping keep
+        them -- and made again for a longer channel list, which takes the states over, or, at rest, for another owner."""
+        C = len(self._bounds)
+        ent = cache.get(key)
+        if ent is None or ent[0] != C or ent[1] is not owner:
+            h = create(C)
+            if ent is not None and ent[1] is owner:
+                p = ctypes.POINTER(ctype)
+                old = np.zeros((ent[0],) + shape, ctype)
+                hip.check(get_state(ent[2].value, old.ctypes.data_as(p), hip.stream()))
+                new = np.zeros((C,) + shape, ctype)
+                new[:min(C, ent[0])] = old[:min(C, ent[0])]
+                hip.check(set_state(h.value, new.ctypes.data_as(p), hip.stream()))
+            ent = cache.put(key, (C, owner, h), self._state_fence)
+        return ent[2].value
+
     def _afilt_handle(self, ch, A):
-        # one handle per (legs, audio rate), sized for all channels: its state slots are addressed by channel index, so
-        # shard and regrouping keep them; a longer channel list takes the states over
-        C, filt = len(self._bounds), self._afilt[0]
-        ent = self._afilt_handles.get((ch, A))
-        if ent is not None and ent[0] == C and ent[1] is filt:
-            return ent[2].value
-        h = filt._create(C, ch, A)
-        if ent is not None and ent[1] is filt:
-            dp = ctypes.POINTER(ctypes.c_double)
-            old = np.zeros((ent[0], ch, len(filt), 2))
-            hip.check(self._lib.rcfm_audio_filter_get_state(ent[2].value, old.ctypes.data_as(dp), hip.stream()))
-            new = np.zeros((C, ch, len(filt), 2))
-            new[:min(C, ent[0])] = old[:min(C, ent[0])]
-            hip.check(self._lib.rcfm_audio_filter_set_state(h.value, new.ctypes.data_as(dp), hip.stream()))
-        if self._state_fence:
-            hip.check(self._lib.rcfm_audio_filter_set_fence(h.value, 1))
-        self._afilt_handles[(ch, A)] = (C, filt, h)
-        return h.value
+        filt = self._afilt[0]               # one handle per (legs, audio rate)
+        return self._channel_states(self._afilt_handles, (ch, A), filt, lambda C: filt._create(C, ch, A), (ch, len(filt), 2),
+                                    ctypes.c_double, self._lib.rcfm_audio_filter_get_state, self._lib.rcfm_audio_filter_set_state)
 
     def _filter_group(self, first, count, audio):
         # behind the group's tone bank on the same stream, in place
@@ -1078,24 +1111,9 @@ class Tuner(Injector):
         return np.concatenate([hip.to_host(m)[:, 1:] for m in frames]).astype(bool)
 
     def _gate_handle(self, A):
-        # one handle per audio rate (the fade's length follows it), sized for all channels: its state slots are addressed
-        # by channel index, so shard and regrouping keep them; a longer channel list takes the states over
-        C, gate = len(self._bounds), self._gate[0]
-        ent = self._gate_handles.get(A)
-        if ent is not None and ent[0] == C and ent[1] is gate:
-            return ent[2].value
-        h = gate._create(C, A)
-        if ent is not None and ent[1] is gate:
-            ip = ctypes.POINTER(ctypes.c_int32)
-            old = np.zeros((ent[0], 2), np.int32)
-            hip.check(self._lib.rcfm_gate_get_state(ent[2].value, old.ctypes.data_as(ip), hip.stream()))
-            new = np.zeros((C, 2), np.int32)
-            new[:min(C, ent[0])] = old[:min(C, ent[0])]
-            hip.check(self._lib.rcfm_gate_set_state(h.value, new.ctypes.data_as(ip), hip.stream()))
-        if self._state_fence:
-            hip.check(self._lib.rcfm_gate_set_fence(h.value, 1))
-        self._gate_handles[A] = (C, gate, h)
-        return h.value
+        gate = self._gate[0]                # one handle per audio rate (the fade's length follows it)
+        return self._channel_states(self._gate_handles, A, gate, lambda C: gate._create(C, A), (2,), ctypes.c_int32,
+                                    self._lib.rcfm_gate_get_state, self._lib.rcfm_gate_set_state)
 
     def _gate_group(self, handle, first, count, audio):
         # behind the group's audio filter on the same stream: frame levels of its channels, the state machine, then the
@@ -1171,7 +1189,7 @@ class Tuner(Injector):
             owner, tables = mixer._split(ranges, len(self._bounds))
             for key in [k for k, e in self._mix_handles.items() if e[1] != self._version]:
                 del self._mix_handles[key]         # the handles of a channel list that is gone
-            ent = self._mix_handles[ranges] = (mixer, self._version, owner, [mixer._create(*t) for t in tables])
+            ent = self._mix_handles.put(ranges, (mixer, self._version, owner, [mixer._create(*t) for t in tables]), self._state_fence)
         return ent[2], [h.value for h in ent[3]]
 
     def _mix_group(self, h, first, count, audio, mask):
@@ -1275,12 +1293,10 @@ class Tuner(Injector):
                 if key is not None:
                     per = [d.discretise(A, L) if d is not None else (np.float32(1.0), np.float32(0.0), 0) for d in per_bus]
                     tables = (key, [p[0] for p in per], [p[1] for p in per], [p[2] for p in per])
-                h = busdyn.create(M, ch_out, L, A, c, k, *tables)
-                if self._state_fence:
-                    hip.check(self._lib.rcfm_busdyn_set_fence(h.value, 1))
-                made.append((L, h))
-            self._busdyn_handles.clear()           # one shape at a time
-            ent = self._busdyn_handles[name] = (self._busdyn, made)
+                made.append((L, busdyn.create(M, ch_out, L, A, c, k, *tables)))
+            ent = self._busdyn_handles.put(name, (self._busdyn, made), self._state_fence)
+            for other in [shape for shape in self._busdyn_handles if shape != name]:
+                del self._busdyn_handles[other]    # one shape at a time
         return [(L, h.value) for L, h in ent[1]]
 
     def _busdyn_group(self, L, h, mixed):
@@ -1527,15 +1543,8 @@ class Tuner(Injector):
         gate (set_gate) closes every channel."""
         for h in self._batched.values():
             hip.check(self._lib.rcfm_demod_reset_state(h.value, hip.stream()))
-        for _, _, h in self._afilt_handles.values():
-            hip.check(self._lib.rcfm_audio_filter_reset(h.value, hip.stream()))
-        for _, _, h in self._gate_handles.values():
-            hip.check(self._lib.rcfm_gate_reset(h.value, hip.stream()))
-        for _, h in self._floor_handles.values():
-            hip.check(self._lib.rcfm_floor_reset(h.value, hip.stream()))
-        for _, made in self._busdyn_handles.values():
-            for _, h in made:
-                hip.check(self._lib.rcfm_busdyn_reset(h.value, hip.stream()))
+        for cache in self._carried.values():
+            cache.reset_states()
 
     def set_kernel_options(self, lds_chain=True, fused_tiles=True, phase_link=True, narrow_tiles=1, ssb_direct=True):
         """Which forms of the kernel chain run_all / run_each may use (rcfm_demod_set_option; no reference
@@ -1615,15 +1624,8 @@ class Tuner(Injector):
         for key, h in self._batched.items():
             if key[0] not in _STATELESS or _key_agc(key) is not None:
                 hip.check(self._lib.rcfm_demod_set_option(h.value, hip.RCFM_OPT_STATE_FENCE, 1))
-        for _, _, h in self._afilt_handles.values():
-            hip.check(self._lib.rcfm_audio_filter_set_fence(h.value, 1))
-        for _, _, h in self._gate_handles.values():
-            hip.check(self._lib.rcfm_gate_set_fence(h.value, 1))
-        for _, h in self._floor_handles.values():
-            hip.check(self._lib.rcfm_floor_set_fence(h.value, 1))
-        for _, made in self._busdyn_handles.values():
-            for _, h in made:
-                hip.check(self._lib.rcfm_busdyn_set_fence(h.value, 1))
+        for cache in self._carried.values():
+            cache.arm()
 
     def _lane_clone(self):
         """A second Tuner over the SAME channel list, demodulator objects and de-emphasis state, with its own device
@@ -1633,27 +1635,23 @@ class Tuner(Injector):
         t._is_lane = True
         t._state_fence = True
         t._state_owner = self._state_owner        # shared, the same dicts: one de-emphasis state per channel, whoever runs it ...
-        t._afilt_handles = self._afilt_handles    # ... and one audio filter state ...
-        t._gate_handles = self._gate_handles      # ... and one frame gate state ...
-        t._floor_handles = self._floor_handles    # ... and one tracked noise floor ...
-        t._mix_handles = self._mix_handles        # ... and the mixer's tables, which hold no state ...
-        t._busdyn_handles = self._busdyn_handles  # ... and one state of the bus dynamics; every other device handle is the lane's own
+        t._carried = self._carried                # ... and one of every carried state, under the same names;
+        t.__dict__.update(self._carried)          # every other device handle is the lane's own
         t._sync_lane(self)
         return t
 
     def _sync_lane(self, base):
         """Follow the base tuner: its settings, each a new object per set_* -- what this lane made from the old one is made
         again when it is next used (_derived), on the lane's own stream -- and its channel list."""
-        if self._tones is not base._tones or self._squelch is not base._squelch or self._gate is not base._gate or \
-                self._mix is not base._mix or self._busdyn is not base._busdyn:
+        drops = {drop for name, drop in _FOLLOWED.items() if getattr(self, name) is not getattr(base, name)}
+        if "last" in drops:
             self._last = _Run()                            # (Lanes keeps each buffer's results with its ticket)
-        self._mix, self._busdyn = base._mix, base._busdyn
-        if self._blanker is not base._blanker:
+        if "blanker" in drops:
             self.set_blanker(None)                         # the handle and scratch of this lane's own go with their blanker
-        if self._floor is not base._floor:
+        if "floor" in drops:
             self._floor_out = None                         # (the handles are shared: the base tuner's set_floor dropped them)
-        self._squelch, self._tones, self._afilt, self._iq_balance, self._blanker, self._fine, self._gate, self._floor = \
-            base._squelch, base._tones, base._afilt, base._iq_balance, base._blanker, base._fine, base._gate, base._floor
+        for name in _FOLLOWED:
+            setattr(self, name, getattr(base, name))
         if self._version == base._version and self._bounds is base._bounds and self._shard == base._shard and \
                 self._input_bandwidth == base._input_bandwidth:
             return
