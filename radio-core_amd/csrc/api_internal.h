@@ -32,10 +32,10 @@ constexpr double kPi = 3.14159265358979323846;
 // Device tables + scalars of one scipy.signal.resample geometry n -> m.
 struct ResampleGeom {
     int64_t n = 0, m = 0;
-    int nmin = 0, nyq = 0, nneg = 0;
+    int nyq = 0, nneg = 0;
     int nyq_mode = NYQ_NONE;   // complex
     float w_merge = 0.f;       // complex, NYQ_DOWN
-    float nyq_factor = 1.f;    // real
+    float nyq_factor = 1.f; int nyq_bin = -1;   // real: resample_nyquist (spectrum_rules.h), -1 = no such bin
     float scale = 1.f;         // (m/n) * 1/m for an unnormalised inverse
     DeviceBuffer wpos, wneg;   // complex: float[nyq], float[nneg + 1]
     DeviceBuffer wr;           // real: float[nyq]

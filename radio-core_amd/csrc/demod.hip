@@ -363,7 +363,7 @@ struct rcfm_demod_s {
 
     // USB / LSB (include/rcfm.h): where the sideband's spectrum comes from, for fused_ssb_ifft.
     SsbSource ssb_source(const float2* X, const int32_t* base32, int64_t N) const {
-        return SsbSource{X, base32, N, B, kind == RCFM_LSB, geom.wr.as<float>(), geom.nyq_factor};
+        return SsbSource{X, base32, N, B, kind == RCFM_LSB, geom.wr.as<float>(), geom.nyq_bin, geom.nyq_factor};
     }
 
     void ssb_tail(int first, int cnt, float* audio, hipStream_t s) {
@@ -419,8 +419,7 @@ struct rcfm_demod_s {
             {
                 StageTimer tm(ST_AUDIO_SPECTRUM, s);
                 launch_ssb_select(buf_Z.as<float2>(), B, buf_V.as<float2>(), A, cnt, geom.wr.as<float>(),
-                                  (int)std::min<int64_t>(A / 2, (B - 1) / 2), (A % 2 == 0 && A < B) ? A / 2 : -1,
-                                  geom.nyq_factor, geom.scale, kind == RCFM_LSB, s);
+                                  (int)std::min<int64_t>(A / 2, (B - 1) / 2), geom.nyq_bin, geom.nyq_factor, geom.scale, kind == RCFM_LSB, s);
             }
             StageTimer tm(ST_IFFT_A, s);
             f2.exec(buf_V.get(), audio, work.get(), s);
@@ -509,7 +508,7 @@ struct rcfm_demod_s {
         }
         {   // unpack + window + Nyquist rule ride on the first pass of IFFT_A
             StageTimer tm(ST_IFFT_A, s);
-            TILE_CALL(nw, fused_stereo_unpack_ifft, *eng_A, Z, B, V, TA, cnt, geom.wr.as<float>(), geom.nyq, geom.nmin,
+            TILE_CALL(nw, fused_stereo_unpack_ifft, *eng_A, Z, B, V, TA, cnt, geom.wr.as<float>(), geom.nyq, geom.nyq_bin,
                       geom.nyq_factor, geom.scale, buf_dc.as<float2>(), s);
             // -> [cnt][A][2] float32, L/R interleaved
         }
@@ -554,7 +553,7 @@ struct rcfm_demod_s {
         }
         {
             StageTimer tm(ST_AUDIO_SPECTRUM, s);
-            launch_stereo_unpack(Z, B, V, A, cnt, geom.wr.as<float>(), geom.nyq, geom.nmin,
+            launch_stereo_unpack(Z, B, V, A, cnt, geom.wr.as<float>(), geom.nyq, geom.nyq_bin,
                                  geom.nyq_factor, geom.scale, nullptr, s);
         }
         {
@@ -598,7 +597,7 @@ struct rcfm_demod_s {
         }
         {
             StageTimer tm(ST_AUDIO_SPECTRUM, s);
-            launch_spectrum_real_full(Dfull, B, Yfull, A, cnt, geom.wr.as<float>(), geom.nyq, geom.nmin,
+            launch_spectrum_real_full(Dfull, B, Yfull, A, cnt, geom.wr.as<float>(), geom.nyq, geom.nyq_bin,
                                       geom.nyq_factor, geom.scale, buf_dc.as<float2>(), true, s);
         }
         {
@@ -621,7 +620,7 @@ struct rcfm_demod_s {
         }
         {
             StageTimer tm(ST_AUDIO_SPECTRUM, s);
-            launch_spectrum_r2c(D, B, Y, A, cnt, geom.wr.as<float>(), geom.nyq, geom.nmin, geom.nyq_factor,
+            launch_spectrum_r2c(D, B, Y, A, cnt, geom.wr.as<float>(), geom.nyq, geom.nyq_bin, geom.nyq_factor,
                                 geom.scale, s);
         }
         StageTimer tm(ST_IFFT_A, s);

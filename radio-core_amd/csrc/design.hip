@@ -20,7 +20,7 @@ double shifted_window(double a0, int64_t n, int64_t k) {
 void ResampleGeom::build(int64_t n_, int64_t m_, double a0, bool complex_input) {
     n = n_;
     m = m_;
-    nmin = (int)std::min(n, m);
+    const int nmin = (int)std::min(n, m);
     nyq = nmin / 2 + 1;
     scale = (float)(1.0 / (double)n);
     const bool even = (nmin % 2) == 0;
@@ -47,9 +47,8 @@ void ResampleGeom::build(int64_t n_, int64_t m_, double a0, bool complex_input) 
             r[k] = (float)w;
         }
         wr.upload(r.data(), r.size() * sizeof(float));
-        nyq_factor = 1.f;
-        if (even && m < n) nyq_factor = 2.f;
-        if (even && n < m) nyq_factor = 0.5f;
+        nyq_bin = resample_nyquist_bin(n, m);
+        nyq_factor = resample_nyquist_factor(n, m);
     }
 }
 

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
     for (int e = tid; e < L2 * W; e += T) {
         const int l = e >> kLogW, wl = e & (W - 1);
         float2 x = tile[lds_slot<true>(l, wl)];
-        if (l == L2 / 2 && i0 + wl == 0) {   // Y[A/2] = X[A/2] + X[-A/2] (one point of one tile)
+        if (l == L2 / 2 && i0 + wl == 0) {   // resample_nyquist (spectrum_rules.h) as a row sum: Y[A/2] = X[A/2] + X[-A/2] (one point of one tile)
             const float2 y = tile[lds_slot<true>(L2, wl)];
             x = make_float2(x.x + y.x, x.y + y.y);
         }

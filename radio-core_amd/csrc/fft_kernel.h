@@ -1503,7 +1503,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
             y[2] = xr[dft_slot<RL>(RL - 2)];      // k = L - L2 / 2 + g: row L2 / 2 + g (g = 0: the negative Nyquist row)
             y[3] = xr[dft_slot<RL>(RL - 1)];
             const bool first = rg == 0 && i0 + w == 0;   // bins kappa = 0 and A / 2: one lane of one tile
-            if (first) y[2] = cadd(y[2], xr[dft_slot<RL>(2)]);   // Y[A/2] = X[A/2] + X[-A/2]
+            if (first) y[2] = cadd(y[2], xr[dft_slot<RL>(2)]);   // resample_nyquist (spectrum_rules.h) as a sum: Y[A/2] = X[A/2] + X[-A/2]
 #pragma unroll
             for (int q = 0; q < 4; ++q) y[q] = make_float2(y[q].x * wgt[q], y[q].y * wgt[q]);
             if (first) {
@@ -1560,7 +1560,7 @@ __global__ __launch_bounds__(T, (T * 16 / W >= 512 ? 4 : 1)) void k_fft_tile2_de
             if ((L2 * W) % T == 0 || e < L2 * W) {
                 const int l = e >> kLogW, wl = e & (W - 1);
                 float2 x = tile[lds_slot<true>(l, wl)];
-                if (l == L2 / 2 && i0 + wl == 0) {   // Y[A/2] = X[A/2] + X[-A/2] (one point of one tile)
+                if (l == L2 / 2 && i0 + wl == 0) {   // resample_nyquist (spectrum_rules.h) as a row sum: Y[A/2] = X[A/2] + X[-A/2] (one point of one tile)
                     const float2 y = tile[lds_slot<true>(L2, wl)];
                     x = make_float2(x.x + y.x, x.y + y.y);
                 }

@@ -44,7 +44,7 @@ struct SsbSource {
     int B;
     bool lower;            // LSB: bin -k, conjugated, in the place of bin +k
     const float* wr;       // Decimate(B -> A)'s folded Hamming weight (ResampleGeom::wr)
-    float nyq_factor;      // ... and its Nyquist factor (applies when A is even and A < B)
+    int nyq_bin; float nyq_factor;   // ... and its Nyquist rule (ResampleGeom)
 };
 
 // fused_real_pair_fft / StorePruned: keep only bins 0 .. n/2 (all the packed Hilbert chain reads)

@@ -19,7 +19,7 @@ namespace {
 // LoadOp::operator() fetches only; LoadOp::post does the arithmetic when the tile is consumed.
 
 // First pass of Tuner.run's inverse FFT: element k of the channel spectrum comes from
-// bin (src - roll) mod N of the wideband spectrum, src = k (k < nyq) or N - (B - k).
+// bin (gather_offset(k) - roll) mod N of the wideband spectrum (spectrum_rules.h).
 // The hot form of the gather below: narrow channels (window argument < 0.25 rad: 4-term cosine
 // series), B <= N (every bin has a source), haloed spectrum (no wrap-around), 32-bit indices.
 // ~12 VALU instructions per element instead of ~30.  (A 2-term series -- enough below 0.029 rad, cfg4 has 0.003 -- measured
@@ -33,14 +33,13 @@ struct LoadTunerGatherFast {
     int merge;              // NYQ_DOWN: the bin (B/2) that also receives X[-B/2]; otherwise -1
     int line_stride;
 
-    __device__ __forceinline__ int source_offset(int k) const { return k < nyq ? k : k - B; }
     __device__ __forceinline__ float window(int d) const {
         const float th = fmaf((float)d, two_pi_over_n, delta);
         const float t = th * th;
         return fmaf(t, fmaf(t, fmaf(t, c3, c2), c1), c0);
     }
     __device__ __forceinline__ float2 fetch(const LineId& id, int l, int64_t, unsigned) const {
-        return X[base[id.batch] + source_offset(l * line_stride + (int)id.i)];
+        return X[base[id.batch] + gather_offset(l * line_stride + (int)id.i, B, nyq)];
     }
     // NYQ_DOWN: Y[+B/2] += X[-B/2] w(-B/2): a workgroup-uniform value that one lane of one tile adds.
     static constexpr bool kCtx = true;
@@ -53,7 +52,7 @@ struct LoadTunerGatherFast {
     }
     __device__ __forceinline__ float2 post(const LineId& id, int l, float2 v, const Ctx& m2) const {
         const int k = l * line_stride + (int)id.i;
-        const float w = window(source_offset(k));
+        const float w = window(gather_offset(k, B, nyq));
         const float sel = (k == merge) ? 1.f : 0.f;
         // inverse transform by the swap identity
         return make_float2(fmaf(sel, m2.y, v.y * w), fmaf(sel, m2.x, v.x * w));
@@ -72,20 +71,6 @@ struct LoadTunerGatherT {
     int line_stride;   // in_l of the pass: k = l * line_stride + i
     int64_t x_batch;   // spectrum of signal c starts at X + c * x_batch (0: one shared spectrum)
 
-    // Signed offset d of the source bin of output bin k (source = d mod N); ok = false: zero fill.
-    // Branch-free per lane; only the nyq_mode tests (kernel arguments) branch, uniformly.
-    __device__ __forceinline__ int source_offset(int k, bool& ok) const {
-        const int j = B - k;
-        const bool pos = k < nyq;
-        int d = pos ? k : -j;
-        ok = pos | (j <= nneg);
-        if (nyq_mode == NYQ_UP) {   // Y[-N/2] = Y[+N/2] / 2
-            const bool up = !ok & (j == nyq - 1);
-            d = up ? nyq - 1 : d;
-            ok |= up;
-        }
-        return ok ? d : 0;
-    }
     __device__ __forceinline__ I rolled(int d, I r) const {   // (d - r) mod N, |d| <= N/2, r in [0, N)
         I i = (I)d - r;
         if (d < 0) i += N;
@@ -108,16 +93,16 @@ struct LoadTunerGatherT {
     }
     __device__ __forceinline__ float2 fetch(const LineId& id, int l, int64_t, unsigned) const {
         bool ok;
-        const int d = source_offset(l * line_stride + (int)id.i, ok);   // the same expression as in post()
+        const int d = gather_offset(l * line_stride + (int)id.i, B, nyq, nneg, nyq_mode, ok);   // (source bin = d mod N)
         return (X + (int64_t)id.batch * x_batch)[rolled(d, (I)roll[id.batch])];
     }
     __device__ __forceinline__ float2 post(const LineId& id, int l, float2 v) const {
         const int k = l * line_stride + (int)id.i;
         bool ok;
-        const int d = source_offset(k, ok);
+        const int d = gather_offset(k, B, nyq, nneg, nyq_mode, ok);
         float w = ok ? window(d) : 0.f;
         const int half = nyq - 1;
-        if (nyq_mode == NYQ_UP) w = (k == half || (B - k) == half) ? 0.5f * w : w;
+        if (nyq_mode == NYQ_UP) w = nyquist_up_halved(k, B, nyq) ? 0.5f * w : w;
         float2 y = make_float2(v.x * w, v.y * w);
         if (nyq_mode == NYQ_DOWN) {   // Y[+N/2] += X[-N/2]: one element per channel
             // workgroup-uniform address and value (hoisted out of the per-element code); lanes select
@@ -206,8 +191,8 @@ LoadPhaseStepPair phase_pair_load(const float* x, int64_t n, int count, int line
     return ld;
 }
 
-// Hilbert mask applied to one member of such a pair: with U = FFT(x0 + j x1),
-// X0[k] = (U[k] + conj U[-k]) / 2, X1[k] = (U[k] - conj U[-k]) / 2j; Z = h X, bins above n/2 are 0.
+// Hilbert mask applied to one member of such a pair (pair_even / pair_odd of U = FFT(x0 + j x1), whose 1 / 2 rides
+// in the mask's unit): Z = h X, bins above n/2 are 0.
 // HZ: the pass is the first of a two-pass plan of even length (point k = l * stride + i, n = L *
 // stride), so the kernel may skip everything above the middle (fft_kernel.h, kHalfZones).
 template <bool HZ>
@@ -231,14 +216,8 @@ struct LoadHilbertPairT {
     }
     __device__ __forceinline__ float2 post(const LineId& id, int l, float2 a, float2 b, int zone = 1) const {
         const int k = l * line_stride + (int)id.i;
-        float h = (k == 0) ? 0.5f : 1.f;   // h / 2 of scipy.signal.hilbert's {1, 2, ..., 2, (1), 0, ...}
-        if (zone != 0) {
-            if (k >= (n + 1) / 2) h = 0.f;
-            if ((n & 1) == 0 && k == n / 2) h = 0.5f;
-        }
-        float2 xk;
-        if ((id.batch & 1) == 0) xk = make_float2(a.x + b.x, a.y - b.y);          // U[k] + conj U[-k]
-        else xk = make_float2(a.y + b.y, -(a.x - b.x));                           // (U[k] - conj U[-k]) / j
+        const float h = zone == 0 ? hilbert_weight_low(k, 0.5f) : hilbert_weight(n, k, 0.5f);
+        const float2 xk = (id.batch & 1) == 0 ? pair_even(a, b) : pair_odd(a, b);
         return make_float2(xk.y * h, xk.x * h);   // swapped: inverse transform
     }
 };
@@ -258,11 +237,7 @@ struct LoadHilbertPackedT {
     }
     __device__ __forceinline__ float2 post(const LineId& id, int l, float2 v, int zone = 1) const {
         const int k = l * line_stride + (int)id.i;
-        float h = (k == 0) ? scale : 2.f * scale;
-        if (zone != 0) {
-            if (k >= (n + 1) / 2) h = 0.f;
-            if ((n & 1) == 0 && k == n / 2) h = scale;
-        }
+        const float h = zone == 0 ? hilbert_weight_low(k, scale) : hilbert_weight(n, k, scale);
         return make_float2(v.y * h, v.x * h);   // swapped: inverse transform
     }
 };
@@ -290,10 +265,7 @@ struct LoadHilbertMask {
     }
     __device__ __forceinline__ float2 post(const LineId& id, int l, float2 v) const {
         const int k = (int)(l * line_stride + id.i);
-        float h = 0.f;
-        if (k == 0) h = 1.f;
-        else if (k < (n + 1) / 2) h = 2.f;
-        else if ((n & 1) == 0 && k == n / 2) h = 1.f;
+        const float h = hilbert_weight(n, k, 1.f);
         return make_float2(v.y * h, v.x * h);   // swapped: inverse transform
     }
 };
@@ -350,9 +322,7 @@ struct MidHilbertMaskT {
     __device__ __forceinline__ float fetch_aux(const LineId&, int, int64_t, unsigned) const { return 0.f; }
     __device__ __forceinline__ float2 operator()(const LineId& id, int k, float2 v, float) const {
         const int bin = k * stride + (int)id.i;
-        float h = (bin == 0) ? scale : 2.f * scale;
-        if (bin >= (n + 1) / 2) h = 0.f;
-        if ((n & 1) == 0 && bin == n / 2) h = scale;
+        const float h = hilbert_weight(n, bin, scale);
         return make_float2(v.y * h, v.x * h);
     }
 };
@@ -389,51 +359,32 @@ struct MidStereoMixPair {
     }
 };
 
-// wbfm.py:86-87 / decimate.py:48 as the load of IFFT_A's first pass: U = FFT_B of the packed signal
-// (m+lmr) + j(m-lmr), pruned to |k| <= A/2; point k of the packed Hermitian pair V = HL + j HR
-// (ifft(V) = l + j r), with the Hamming weight, truncation and Nyquist rule of scipy.signal.resample.
+// stereo_unpack_point (spectrum_rules.h) as the load of IFFT_A's first pass: U = FFT_B of the packed signal
+// (m+lmr) + j(m-lmr), pruned to |k| <= A/2.
 struct LoadStereoUnpack {
     static constexpr int kFetches = 3;
     const float2* U;      // [count][B]
     const float* wr;      // folded window, nyq entries
     float2* dc;           // [count] or null: receives V[c][0] = (sum l, sum r) / A
-    int B, A, nyq, nmin;
+    int B, A, nyq, nyq_bin;
     float nyq_factor, scale;
     int line_stride;
-    __device__ __forceinline__ int folded(int k) const { return k > A / 2 ? A - k : k; }
     __device__ __forceinline__ float2 fetch(const LineId& id, int l, int64_t, unsigned) const {
-        const int kk = folded(l * line_stride + (int)id.i);
+        const int kk = fold(l * line_stride + (int)id.i, A).kk;
         return (U + (int64_t)id.batch * B)[kk < nyq ? kk : 0];
     }
     __device__ __forceinline__ float2 fetch2(const LineId& id, int l, int64_t, unsigned) const {
-        const int kk = folded(l * line_stride + (int)id.i);
+        const int kk = fold(l * line_stride + (int)id.i, A).kk;
         return (U + (int64_t)id.batch * B)[(kk < nyq && kk > 0) ? B - kk : 0];
     }
     __device__ __forceinline__ float fetch3(const LineId& id, int l, int64_t, unsigned) const {
-        const int kk = folded(l * line_stride + (int)id.i);
+        const int kk = fold(l * line_stride + (int)id.i, A).kk;
         return wr[kk < nyq ? kk : 0];
     }
     __device__ __forceinline__ float2 post(const LineId& id, int l, float2 a, float2 b, float w0) const {
         const int k = l * line_stride + (int)id.i;
-        const bool mirrored = k > A / 2;
-        const int kk = mirrored ? A - k : k;
-        float2 hl = make_float2(0.f, 0.f), hr = make_float2(0.f, 0.f);
-        if (kk < nyq) {
-            // u = l + j r with l, r real  =>  L[k] = (U[k] + conj U[-k]) / 2,  R[k] = (U[k] - conj U[-k]) / 2j
-            float w = w0 * scale;
-            if ((nmin & 1) == 0 && kk == nmin / 2) w *= nyq_factor;
-            hl = make_float2(0.5f * (a.x + b.x) * w, 0.5f * (a.y - b.y) * w);
-            hr = make_float2(0.5f * (a.y + b.y) * w, -0.5f * (a.x - b.x) * w);
-            if (kk == 0 || ((A & 1) == 0 && kk == A / 2)) {
-                hl.y = 0.f;
-                hr.y = 0.f;
-            }
-        }
-        if (mirrored) {
-            hl.y = -hl.y;
-            hr.y = -hr.y;
-        }
-        const float2 out = make_float2(hl.x - hr.y, hl.y + hr.x);
+        const auto f = fold(k, A);
+        const float2 out = stereo_unpack_point(a, b, w0 * scale, f, f.kk < nyq, nyq_bin, nyq_factor, A);
         if (k == 0 && dc != nullptr) dc[id.batch] = out;   // one lane of one tile per channel
         return make_float2(out.y, out.x);                  // swapped: inverse transform
     }
@@ -838,12 +789,12 @@ void fused_fft_decim_ifft_pairs(const FftEngine& ef, const FftEngine& ea, const 
 }
 
 void fused_stereo_unpack_ifft(const FftEngine& e, const float2* U, int64_t B, float2* out, float2* tmp, int count,
-                              const float* wr, int nyq, int nmin, float nyq_factor, float scale, float2* dc,
+                              const float* wr, int nyq, int nyq_bin, float nyq_factor, float scale, float2* dc,
                               hipStream_t s) {
     if (count <= 0) return;
     const int64_t A = e.desc().n;
     const int np = e.npass();
-    LoadStereoUnpack ld{U, wr, dc, (int)B, (int)A, nyq, nmin, nyq_factor, scale, (int)e.desc().pass[0].in_l};
+    LoadStereoUnpack ld{U, wr, dc, (int)B, (int)A, nyq, nyq_bin, nyq_factor, scale, (int)e.desc().pass[0].in_l};
     fftk::StorePlainT<false> st0{tmp, 1.0f};
     fftk::launch_fft_pass<kStridedOnly>(e.pass_dev(0, 0, e.tmp_stride()), count, ld, st0, s);
     middle_passes(e, 1, np - 2, tmp, count, s);
@@ -893,46 +844,41 @@ struct LoadSsbPairT {
     float c0, c1, c2, c3;   // 0.5 + 0.5 cos(th) = c0 + t c1 + t^2 c2 + t^3 c3, t = th^2
     int B, A, count;
     int kmax;               // bins 1 .. kmax of the sideband survive: min(A / 2, (B - 1) / 2)
-    int nyq_bin;            // A / 2 when A is even and A < B (Decimate's Nyquist rule), else -1
+    int nyq_bin;            // Decimate's Nyquist rule (ResampleGeom::nyq_bin)
     float nyq_factor, scale;
     int lower;
     int line_stride;
 
-    __device__ __forceinline__ int folded(int k) const { return k > A / 2 ? A - k : k; }
-    __device__ __forceinline__ bool kept(int kk) const { return kk >= 1 && kk <= kmax; }
     // element of channel c that holds sideband bin kk (bin 0 -- always readable -- for a dropped one)
     __device__ __forceinline__ float2 bin(int c, int kk) const {
-        const int q = kept(kk) ? (lower ? -kk : kk) : 0;
+        const int q = ssb_kept(kk, kmax) ? (lower ? -kk : kk) : 0;
         if (DIRECT) return X[base[c] + q];
         return (X + (int64_t)c * B)[q < 0 ? B + q : q];
     }
     __device__ __forceinline__ float2 fetch(const LineId& id, int l, int64_t, unsigned) const {
-        return bin(2 * id.batch, folded(l * line_stride + (int)id.i));
+        return bin(2 * id.batch, fold(l * line_stride + (int)id.i, A).kk);
     }
     __device__ __forceinline__ float2 fetch2(const LineId& id, int l, int64_t, unsigned) const {
         const int c1 = 2 * id.batch + 1;
-        return bin(c1 < count ? c1 : c1 - 1, folded(l * line_stride + (int)id.i));
+        return bin(c1 < count ? c1 : c1 - 1, fold(l * line_stride + (int)id.i, A).kk);
     }
     __device__ __forceinline__ float fetch3(const LineId& id, int l, int64_t, unsigned) const {
-        const int kk = folded(l * line_stride + (int)id.i);
-        return wr[kept(kk) ? kk : 0];
+        const int kk = fold(l * line_stride + (int)id.i, A).kk;
+        return wr[ssb_kept(kk, kmax) ? kk : 0];
     }
     __device__ __forceinline__ float2 post(const LineId& id, int l, float2 a, float2 b, float w0) const {
         const int k = l * line_stride + (int)id.i;
-        const bool mirrored = k > A / 2;
-        const int kk = mirrored ? A - k : k;
-        float w = kept(kk) ? w0 * scale : 0.f;
+        const auto f = fold(k, A);
+        float w0s = w0 * scale;
         if (DIRECT) {
-            const float th = fmaf((float)(lower ? -kk : kk), two_pi_over_n, delta);
+            const float th = fmaf((float)(lower ? -f.kk : f.kk), two_pi_over_n, delta);
             const float t = th * th;
-            w *= fmaf(t, fmaf(t, fmaf(t, c3, c2), c1), c0);
+            w0s *= fmaf(t, fmaf(t, fmaf(t, c3, c2), c1), c0);
         }
-        if (kk == nyq_bin) w *= nyq_factor;
-        // conj for LSB, conj again for the mirrored half; the Nyquist bin of a real signal is real
-        const float sgn = (kk == nyq_bin) ? 0.f : ((lower != 0) != mirrored ? -w : w);
+        const float2 w = ssb_weights(w0s, f.kk, kmax, f.mirrored, lower != 0, nyq_bin, nyq_factor);
         const float w1 = (2 * id.batch + 1 < count) ? 1.f : 0.f;   // an odd last channel rides alone
-        const float2 y0 = make_float2(a.x * w, a.y * sgn);
-        const float2 y1 = make_float2(b.x * w * w1, b.y * sgn * w1);
+        const float2 y0 = make_float2(a.x * w.x, a.y * w.y);
+        const float2 y1 = make_float2(b.x * w.x * w1, b.y * w.y * w1);
         // Z = Y0 + j Y1, handed on with re / im exchanged: inverse transform by the swap identity
         return make_float2(y0.y + y1.x, y0.x - y1.y);
     }
@@ -944,7 +890,6 @@ void fused_ssb_ifft(const FftEngine& e, const SsbSource& src, float* y, float2* 
     const int np = e.npass();
     const int pairs = (count + 1) / 2;
     const int kmax = (int)std::min<int64_t>(A / 2, (src.B - 1) / 2);
-    const int nyq_bin = (A % 2 == 0 && A < src.B) ? (int)(A / 2) : -1;
     fftk::StorePlainT<false> st0{tmp, 1.0f};
     auto first_pass = [&](auto ld) {
         ld.X = src.X;
@@ -960,7 +905,7 @@ void fused_ssb_ifft(const FftEngine& e, const SsbSource& src, float* y, float2* 
         ld.A = (int)A;
         ld.count = count;
         ld.kmax = kmax;
-        ld.nyq_bin = nyq_bin;
+        ld.nyq_bin = src.nyq_bin;
         ld.nyq_factor = src.nyq_factor;
         // irfft's 1 / A, Decimate's A / B and -- from the wideband spectrum -- the Tuner's B / N
         ld.scale = (float)(1.0 / (double)(src.base32 ? src.N : (int64_t)src.B));

@@ -92,7 +92,7 @@ void fused_fft_decim_ifft_pairs(const FftEngine& ef, const FftEngine& ea, const 
 // the Nyquist rule of decimate.py:48 are the load of IFFT_A's first pass; out [count][A] = l + j r
 // (= float32 [count][A][2]).  dc (optional, [count]) receives (sum l, sum r) / A.  e is the length-A plan.
 void fused_stereo_unpack_ifft(const FftEngine& e, const float2* U, int64_t B, float2* out, float2* tmp, int count,
-                              const float* wr, int nyq, int nmin, float nyq_factor, float scale, float2* dc,
+                              const float* wr, int nyq, int nyq_bin, float nyq_factor, float scale, float2* dc,
                               hipStream_t s);
 
 // Forward FFT whose last pass stores only the bins |k| <= keep (decimation to A needs no more).

@@ -3,12 +3,9 @@
 #pragma once
 
 #include "common.h"
+#include "spectrum_rules.h"
 
 namespace rcfm {
-
-// How scipy.signal.resample treats the Nyquist bin when min(n, m) is even
-// (scipy 1.15.3 _signaltools.py, "Split/join Nyquist component(s)").
-enum NyquistMode : int { NYQ_NONE = 0, NYQ_DOWN = 1, NYQ_UP = 2 };
 
 // Y[c][k] (m bins) <- roll + window + truncate/zero-pad of X[c][.] (n bins), complex
 // spectra.  Shared by Tuner.run (tuner.py:159-161, x_stride = 0: every channel reads
@@ -21,16 +18,16 @@ void launch_spectrum_c2c(const float2* X, int64_t x_stride, int64_t n, const int
                          int nyq, int nneg, int nyq_mode, float scale, hipStream_t stream);
 
 // Half-spectrum version for real signals (FM/MFM audio decimation, real Decimate):
-// X [batch][n/2+1] -> Y [batch][m/2+1]; wr = folded window, nyq_factor = 2, 0.5 or 1.
+// X [batch][n/2+1] -> Y [batch][m/2+1]; wr = folded window; nyq_bin, nyq_factor: ResampleGeom.
 void launch_spectrum_r2c(const float2* X, int64_t n, float2* Y, int64_t m, int batch, const float* wr,
-                         int nyq, int nmin, float nyq_factor, float scale, hipStream_t stream);
+                         int nyq, int nyq_bin, float nyq_factor, float scale, hipStream_t stream);
 
 // Same resampling rule, but from the FULL complex spectrum X [batch][n] of a real signal to
 // the full Hermitian spectrum Y [batch][m] (feeds a complex inverse FFT whose real part is y).
 // dc (optional, [batch]): receives Y[c][0], the DC bin (sum of the resampled signal / m).
 // paired: X is [ceil(batch/2)][n], one complex FFT per pair of real signals (x[2p] + j x[2p+1]).
 void launch_spectrum_real_full(const float2* X, int64_t n, float2* Y, int64_t m, int batch, const float* wr,
-                               int nyq, int nmin, float nyq_factor, float scale, float2* dc, bool paired,
+                               int nyq, int nyq_bin, float nyq_factor, float scale, float2* dc, bool paired,
                                hipStream_t stream);
 
 // scipy.signal.hilbert's mask (pll.py:34): P [batch][n/2+1] half spectrum of the real
@@ -43,7 +40,7 @@ void launch_hilbert_mask(const float2* P, float2* Z, int64_t n, int batch, float
 // l + j r, with the Hamming weight, truncation and Nyquist rule of decimate.py:48.
 // dc (optional, [batch]): receives V[c][0] = (sum l, sum r) / A.
 void launch_stereo_unpack(const float2* U, int64_t B, float2* V, int64_t A, int batch, const float* wr,
-                          int nyq, int nmin, float nyq_factor, float scale, float2* dc, hipStream_t stream);
+                          int nyq, int nyq_bin, float nyq_factor, float scale, float2* dc, hipStream_t stream);
 
 // fm.py:60-65: d[0] = 0, d[i] = arg(x[i] conj(x[i-1])) / pi.
 void launch_discriminator(const float2* iq, float* d, int64_t n, int batch, hipStream_t stream);

@@ -44,23 +44,16 @@ __global__ __launch_bounds__(kThreads) void k_spectrum_c2c(
         if (i < 0) i += n;
         return Xc[i];
     };
-    const int64_t half = nyq - 1;  // min(n, m) / 2
     float2 y = make_float2(0.f, 0.f);
-    if (k < nyq) {
-        y = cscale(fetch(k), wpos[k]);
-        if (k == half && nyq_mode == NYQ_DOWN) {  // Y[+N/2] += X[-N/2]
-            float2 v = cscale(fetch(n - half), w_merge);
+    bool ok;
+    const int64_t d = gather_offset(k, m, nyq, nneg, nyq_mode, ok);
+    if (ok) {
+        y = d >= 0 ? cscale(fetch(d), wpos[d]) : cscale(fetch(n + d), wneg[-d]);
+        if (nyq_mode == NYQ_UP && nyquist_up_halved(k, m, nyq)) y = cscale(y, 0.5f);
+        if (nyq_mode == NYQ_DOWN && k == nyq - 1) {  // Y[+N/2] += X[-N/2]
+            float2 v = cscale(fetch(n - k), w_merge);
             y.x += v.x;
             y.y += v.y;
-        } else if (k == half && nyq_mode == NYQ_UP) {
-            y = cscale(y, 0.5f);
-        }
-    } else {
-        const int64_t j = m - k;
-        if (j <= nneg) {
-            y = cscale(fetch(n - j), wneg[j]);
-        } else if (nyq_mode == NYQ_UP && j == half) {  // Y[-N/2] = Y[+N/2]
-            y = cscale(fetch(half), 0.5f * wpos[half]);
         }
     }
     Y[(int64_t)c * m + k] = cscale(y, scale);
@@ -68,51 +61,44 @@ __global__ __launch_bounds__(kThreads) void k_spectrum_c2c(
 
 __global__ __launch_bounds__(kThreads) void k_spectrum_r2c(const float2* __restrict__ X, int64_t n,
                                                            float2* __restrict__ Y, int64_t m,
-                                                           const float* __restrict__ wr, int nyq, int nmin,
+                                                           const float* __restrict__ wr, int nyq, int nyq_bin,
                                                            float nyq_factor, float scale) {
     const int c = blockIdx.y;
     const int64_t mh = m / 2 + 1;
     const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (k >= mh) return;
     float2 y = make_float2(0.f, 0.f);
-    if (k < nyq) {
-        y = cscale(X[(int64_t)c * (n / 2 + 1) + k], wr[k]);
-        if ((nmin & 1) == 0 && k == nmin / 2) y = cscale(y, nyq_factor);
-    }
-    // A real inverse transform never sees the imaginary part of DC / Nyquist
-    // (pocketfft's c2r drops it); make that explicit for any backend.
-    if (k == 0 || ((m & 1) == 0 && k == m / 2)) y.y = 0.f;
+    if (k < nyq) y = resample_nyquist(cscale(X[(int64_t)c * (n / 2 + 1) + k], wr[k]), k, nyq_bin, nyq_factor);
+    if (real_bin_is_real(k, m)) y.y = 0.f;   // explicit for any backend
     Y[(int64_t)c * mh + k] = cscale(y, scale);
 }
 
 // paired != 0: X holds FFT(x[2p] + j x[2p+1]) per pair p (two real signals per transform); channel c
-// takes X_c[k] = (U[k] + conj U[-k]) / 2 (even c) or (U[k] - conj U[-k]) / 2j (odd c).
+// takes member c & 1 of pair c >> 1.
 __global__ __launch_bounds__(kThreads) void k_spectrum_real_full(const float2* __restrict__ X, int64_t n,
                                                                  float2* __restrict__ Y, int64_t m,
-                                                                 const float* __restrict__ wr, int nyq, int nmin,
+                                                                 const float* __restrict__ wr, int nyq, int nyq_bin,
                                                                  float nyq_factor, float scale,
                                                                  float2* __restrict__ dc, int paired) {
     const int c = blockIdx.y;
     const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (k >= m) return;
-    const bool mirrored = k > m / 2;
-    const int64_t kk = mirrored ? m - k : k;
+    const auto f = fold(k, m);
+    const int64_t kk = f.kk;
     float2 y = make_float2(0.f, 0.f);
     if (kk < nyq) {
         float2 xk;
         if (paired) {
             const float2* U = X + (int64_t)(c >> 1) * n;
             const float2 a = U[kk], b = U[kk == 0 ? 0 : n - kk];
-            xk = (c & 1) ? make_float2(0.5f * (a.y + b.y), -0.5f * (a.x - b.x))
-                         : make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
+            xk = cscale((c & 1) ? pair_odd(a, b) : pair_even(a, b), 0.5f);
         } else {
             xk = X[(int64_t)c * n + kk];
         }
-        y = cscale(xk, wr[kk] * scale);
-        if ((nmin & 1) == 0 && kk == nmin / 2) y = cscale(y, nyq_factor);
-        if (kk == 0 || ((m & 1) == 0 && kk == m / 2)) y.y = 0.f;
+        y = resample_nyquist(cscale(xk, wr[kk] * scale), kk, nyq_bin, nyq_factor);
+        if (real_bin_is_real(kk, m)) y.y = 0.f;
     }
-    if (mirrored) y.y = -y.y;
+    if (f.mirrored) y.y = -y.y;
     Y[(int64_t)c * m + k] = y;
     if (k == 0 && dc != nullptr) dc[c] = y;
 }
@@ -123,48 +109,22 @@ __global__ __launch_bounds__(kThreads) void k_hilbert_mask(const float2* __restr
     const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (k >= n) return;
     const float2* Pc = P + (int64_t)c * (n / 2 + 1);
-    float2 v = make_float2(0.f, 0.f);
-    if (k == 0) {
-        v = Pc[0];
-    } else if (k < (n + 1) / 2) {
-        v = cscale(Pc[k], 2.f);
-    } else if ((n & 1) == 0 && k == n / 2) {
-        v = Pc[k];
-    }
-    Z[(int64_t)c * n + k] = cscale(v, scale);
+    Z[(int64_t)c * n + k] = k <= n / 2 ? cscale(Pc[k], hilbert_weight(n, k, scale)) : make_float2(0.f, 0.f);
 }
 
 __global__ __launch_bounds__(kThreads) void k_stereo_unpack(const float2* __restrict__ U, int64_t B,
                                                             float2* __restrict__ V, int64_t A,
-                                                            const float* __restrict__ wr, int nyq, int nmin,
+                                                            const float* __restrict__ wr, int nyq, int nyq_bin,
                                                             float nyq_factor, float scale,
                                                             float2* __restrict__ dc) {
     const int c = blockIdx.y;
     const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (k >= A) return;
     const float2* Uc = U + (int64_t)c * B;
-    const bool mirrored = k > A / 2;
-    const int64_t kk = mirrored ? A - k : k;
-    float2 hl = make_float2(0.f, 0.f), hr = make_float2(0.f, 0.f);
-    if (kk < nyq) {
-        // u = l + j r with l, r real  =>  L[k] = (U[k] + conj U[-k]) / 2,  R[k] = (U[k] - conj U[-k]) / 2j
-        const float2 a = Uc[kk];
-        const float2 b = Uc[kk == 0 ? 0 : B - kk];
-        float w = wr[kk] * scale;
-        if ((nmin & 1) == 0 && kk == nmin / 2) w *= nyq_factor;
-        hl = make_float2(0.5f * (a.x + b.x) * w, 0.5f * (a.y - b.y) * w);
-        hr = make_float2(0.5f * (a.y + b.y) * w, -0.5f * (a.x - b.x) * w);
-        if (kk == 0 || ((A & 1) == 0 && kk == A / 2)) {
-            hl.y = 0.f;
-            hr.y = 0.f;
-        }
-    }
-    if (mirrored) {
-        hl.y = -hl.y;
-        hr.y = -hr.y;
-    }
-    // packed Hermitian pair: V = HL + j HR  ->  ifft(V) = l + j r
-    const float2 out = make_float2(hl.x - hr.y, hl.y + hr.x);
+    const auto f = fold(k, A);
+    const bool live = f.kk < nyq;   // (a dead bin reads bin 0 and drops it, like LoadStereoUnpack)
+    const float2 a = Uc[live ? f.kk : 0], b = Uc[live && f.kk > 0 ? B - f.kk : 0];
+    const float2 out = stereo_unpack_point(a, b, wr[live ? f.kk : 0] * scale, f, live, nyq_bin, nyq_factor, A);
     V[(int64_t)c * A + k] = out;
     if (k == 0 && dc != nullptr) dc[c] = out;   // sum_n l[n] = A Re V[0], sum_n r[n] = A Im V[0]
 }
@@ -222,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void k_pilot_stage(const float2* __restri
             const int64_t q = q0 + s;
             float v = 0.f;
             if (q >= 0 && q < n) {
-                v = 0.54f * d_s[s + 1] + side_tap * (d_s[s] + d_s[s + 2]);
+                v = hamming3(d_s[s], d_s[s + 1], d_s[s + 2], side_tap);
                 if (q >= t0 && q < t0 + T) m_out[(int64_t)c * n + q] = v;
             }
             m_s[s] = v;
@@ -347,7 +307,7 @@ __global__ __launch_bounds__(THREADS) void k_pilot_stage_h40(const IN* __restric
         for (int it = 0; it < (T + 2 * H + THREADS - 1) / THREADS; ++it) {
             const int s = tid + THREADS * it;
             if (s < T + 2 * H) {
-                m_s[mpos(s)] = 0.54f * d_s[s + 1] + side_tap * (d_s[s] + d_s[s + 2]);
+                m_s[mpos(s)] = hamming3(d_s[s], d_s[s + 1], d_s[s + 2], side_tap);
             }
         }
     } else {
@@ -374,7 +334,7 @@ __global__ __launch_bounds__(THREADS) void k_pilot_stage_h40(const IN* __restric
             const int q = q0 + s;
             float v = 0.f;
             if (q >= 0 && q < n32) {
-                v = 0.54f * d_s[s + 1] + side_tap * (d_s[s] + d_s[s + 2]);
+                v = hamming3(d_s[s], d_s[s + 1], d_s[s + 2], side_tap);
                 if (!BLK && q >= t0 && q < t0 + T) m_out[(int64_t)c * n + q] = v;
             }
             m_s[mpos(s)] = v;
@@ -922,9 +882,8 @@ __global__ __launch_bounds__(kThreads) void k_am_tail(float* __restrict__ y, int
 }
 
 // SSB (RCFM_USB / RCFM_LSB) between rocFFT's transforms: X [batch][n] = FFT_n of the channel samples -> the half
-// spectrum Y [batch][m / 2 + 1] of the resampled sideband signal.  Bin k of s = Re(ifft(H X)) is X[k] (USB) or
-// conj X[n - k] (LSB) for 1 <= k <= kmax = min(m / 2, (n - 1) / 2) and zero elsewhere (DC and the bin n / 2 are dropped);
-// then Decimate's folded Hamming weight wr, its Nyquist rule at k = nyq_bin (m even, m < n; else -1), and `scale`.
+// spectrum Y [batch][m / 2 + 1] of the resampled sideband signal: ssb_weights (spectrum_rules.h, kmax = min(m / 2,
+// (n - 1) / 2)) on X[k] (USB) or X[n - k] (LSB), with Decimate's folded Hamming weight wr, its Nyquist rule and `scale`.
 __global__ __launch_bounds__(kThreads) void k_ssb_select(const float2* __restrict__ X, int64_t n, float2* __restrict__ Y,
                                                          int64_t m, const float* __restrict__ wr, int kmax, int nyq_bin,
                                                          float nyq_factor, float scale, int lower) {
@@ -933,10 +892,10 @@ __global__ __launch_bounds__(kThreads) void k_ssb_select(const float2* __restric
     const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (k >= mh) return;
     float2 y = make_float2(0.f, 0.f);
-    if (k >= 1 && k <= kmax) {
-        y = cscale(X[(int64_t)c * n + (lower ? n - k : k)], wr[k] * scale);
-        if (lower) y.y = -y.y;
-        if (k == nyq_bin) y = make_float2(y.x * nyq_factor, 0.f);   // a real inverse transform never sees its imaginary part
+    if (ssb_kept(k, kmax)) {
+        const float2 x = X[(int64_t)c * n + (lower ? n - k : k)];
+        const float2 w = ssb_weights(wr[k] * scale, k, kmax, false, lower != 0, nyq_bin, nyq_factor);
+        y = make_float2(x.x * w.x, x.y * w.y);
     }
     Y[(int64_t)c * mh + k] = y;
 }
@@ -1451,19 +1410,19 @@ void launch_spectrum_c2c(const float2* X, int64_t x_stride, int64_t n, const int
 }
 
 void launch_spectrum_r2c(const float2* X, int64_t n, float2* Y, int64_t m, int batch, const float* wr,
-                         int nyq, int nmin, float nyq_factor, float scale, hipStream_t stream) {
+                         int nyq, int nyq_bin, float nyq_factor, float scale, hipStream_t stream) {
     if (batch <= 0) return;
     hipLaunchKernelGGL(k_spectrum_r2c, grid2(m / 2 + 1, kThreads, batch), dim3(kThreads), 0, stream, X, n, Y,
-                       m, wr, nyq, nmin, nyq_factor, scale);
+                       m, wr, nyq, nyq_bin, nyq_factor, scale);
     RC_LAUNCH_CHECK();
 }
 
 void launch_spectrum_real_full(const float2* X, int64_t n, float2* Y, int64_t m, int batch, const float* wr,
-                               int nyq, int nmin, float nyq_factor, float scale, float2* dc, bool paired,
+                               int nyq, int nyq_bin, float nyq_factor, float scale, float2* dc, bool paired,
                                hipStream_t stream) {
     if (batch <= 0) return;
     hipLaunchKernelGGL(k_spectrum_real_full, grid2(m, kThreads, batch), dim3(kThreads), 0, stream, X, n, Y, m,
-                       wr, nyq, nmin, nyq_factor, scale, dc, paired ? 1 : 0);
+                       wr, nyq, nyq_bin, nyq_factor, scale, dc, paired ? 1 : 0);
     RC_LAUNCH_CHECK();
 }
 
@@ -1475,10 +1434,10 @@ void launch_hilbert_mask(const float2* P, float2* Z, int64_t n, int batch, float
 }
 
 void launch_stereo_unpack(const float2* U, int64_t B, float2* V, int64_t A, int batch, const float* wr,
-                          int nyq, int nmin, float nyq_factor, float scale, float2* dc, hipStream_t stream) {
+                          int nyq, int nyq_bin, float nyq_factor, float scale, float2* dc, hipStream_t stream) {
     if (batch <= 0) return;
     hipLaunchKernelGGL(k_stereo_unpack, grid2(A, kThreads, batch), dim3(kThreads), 0, stream, U, B, V, A, wr,
-                       nyq, nmin, nyq_factor, scale, dc);
+                       nyq, nyq_bin, nyq_factor, scale, dc);
     RC_LAUNCH_CHECK();
 }
 

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "device_math.h"
 #include "fft_kernel.h"
+#include "spectrum_rules.h"
 
 namespace rcfm {
 
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(T) void k_fm_lds(ChainDev p) {
                 k = tid + T * it;
                 k = k < B ? k : B - 1;                          // ragged last sweep: clamped, not stored
             }
-            v[it] = Xc[k < p.a.nyq ? k : k - B];
+            v[it] = Xc[gather_offset<B>(k, p.a.nyq)];
         }
         x2 = Xc[p.a.merge >= 0 ? -p.a.merge : 0];               // Y[+B/2] += X[-B/2] w(-B/2) (NYQ_DOWN)
     };
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(T) void k_fm_lds(ChainDev p) {
 #pragma unroll
                 for (int q = 0; q < R0; ++q) {
                     const int k = tid + M0 * q;
-                    const float w = window(k < p.a.nyq ? k : k - B);
+                    const float w = window(gather_offset<B>(k, p.a.nyq));
                     const float sel = (k == p.a.merge) ? 1.f : 0.f;
                     u[q] = make_float2(fmaf(sel, m2.y, v[q].y * w), fmaf(sel, m2.x, v[q].x * w));   // swapped
                 }
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(T) void k_fm_lds(ChainDev p) {
             for (int it = 0; it < NV; ++it) {
                 const int k = tid + T * it;
                 if (k < B) {
-                    const float w = window(k < p.a.nyq ? k : k - B);
+                    const float w = window(gather_offset<B>(k, p.a.nyq));
                     const float sel = (k == p.a.merge) ? 1.f : 0.f;
                     xs[k] = make_float2(fmaf(sel, m2.y, v[it].y * w), fmaf(sel, m2.x, v[it].x * w));   // swapped
                 }
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(T) void k_fm_lds(ChainDev p) {
         }
     }
     lds_barrier();
-    if (tid == 0) {
+    if (tid == 0) {   // resample_nyquist (spectrum_rules.h) as a sum of the two Nyquist bins
         const float2 a = xs[A / 2], b = xs[A];
         xs[A / 2] = make_float2(a.x + b.x, a.y + b.y);
     }

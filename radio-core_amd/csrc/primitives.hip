@@ -179,7 +179,7 @@ int rcfm_resampler_run(rcfm_resampler_t r, const void* in, void* out, void* stre
         } else {
             r->fwd->exec(const_cast<void*>(in), r->spec_in.get(), r->work.get(), s);
             launch_spectrum_r2c(r->spec_in.as<float2>(), r->n, r->spec_out.as<float2>(), r->m, r->C,
-                                g.wr.as<float>(), g.nyq, g.nmin, g.nyq_factor, g.scale, s);
+                                g.wr.as<float>(), g.nyq, g.nyq_bin, g.nyq_factor, g.scale, s);
             r->inv->exec(r->spec_out.get(), out, r->work.get(), s);
         }
     });
