@@ -7,6 +7,7 @@
 
 #include "agc.h"
 #include "api_internal.h"
+#include "pair_scale.h"
 
 using namespace rcfm;
 
@@ -84,6 +85,7 @@ struct rcfm_demod_s {
     }
     bool narrow(int cnt) const { return eng_B && narrow_launch(*eng_B, cnt, opt_narrow); }
     DeviceBuffer work, buf_iq, buf_m, buf_p, buf_P, buf_Z, buf_V, buf_v, partial, buf_T, buf_TA, buf_U2, buf_dc;
+    DeviceBuffer buf_scale;   // AM / USB / LSB on the engine: [2][chunk] per-row powers of two and their inverses (pair_scale.h)
     int tiles = 0;
 
     // Length A as (A / n_1, n_1), n_1 = eb's first pass length, so that its first pass tiles like eb's last and the
@@ -108,9 +110,12 @@ struct rcfm_demod_s {
     float agc_level = 0.f, agc_floor = 0.f;
     bool carries_state() const { return stateful() || agc_on; }
     size_t state_stride() const { return stateful() ? (size_t)ch * 50 : 1; }   // floats per channel
-    void agc_tail(int first, int cnt, float* audio, hipStream_t s) {
+    // scale_chunk: the rows of `audio` still carry the pair scaling of a chunk of that many channels (0: none); it comes
+    // out first, exactly, so that the follower and the state it carries stay in the signal's own units.
+    void agc_tail(int first, int cnt, float* audio, hipStream_t s, int scale_chunk) {
         StreamFence::Scope fenced(state_buf->fence, s);
         StageTimer tm(kind == RCFM_AM ? ST_AM_TAIL : ST_SSB_TAIL, s);
+        if (scale_chunk) launch_rows_rescale(audio, A, cnt, buf_scale.as<float>() + scale_chunk, s);
         launch_agc_tail(kind == RCFM_AM ? RCFM_AGC_CARRIER : RCFM_AGC_PEAK, audio, audio, A, cnt,
                         agc_params(agc_decay, agc_level, agc_floor), state_at(first), s);
     }
@@ -128,6 +133,7 @@ struct rcfm_demod_s {
                 buf_TA.reset(((c + 1) / 2) * eng_A->tmp_stride() * sizeof(float2));
             }
             if (eng_A && fft_plan_describe(B, &probe)) eng_B = std::make_unique<FftEngine>(B);
+            if (eng_A) buf_scale.reset(2 * c * sizeof(float));
             return;
         }
         if (kind == RCFM_WBFM) {
@@ -169,6 +175,7 @@ struct rcfm_demod_s {
             }
             buf_T.reset(c * eng_B->tmp_stride() * sizeof(float2));
             buf_TA.reset(c * eng_A->tmp_stride() * sizeof(float2));
+            if (kind == RCFM_AM) buf_scale.reset(2 * c * sizeof(float));
             if (kind == RCFM_WBFM) {
                 buf_U2.reset(((c + 1) / 2) * B * sizeof(float2));
                 const FftPlanDesc& pd = eng_B->desc();
@@ -347,28 +354,48 @@ struct rcfm_demod_s {
     // AM (include/rcfm.h, RCFM_AM): envelope |x| into buf_m -- unless the tuner's last pass already stored it there
     // (envelope_ready, rcfm_pipeline_run) --, FM's real-signal routes straight into the audio, then the carrier
     // normalisation in place.  Its mean comes from the DC bin when the route left one.
+    // The engine routes transform the envelopes two by two, and envelopes stand at their stations' RF levels: each row
+    // is brought to [1, 2) by a power of two first (pair_scale.h), which the division by the row's mean cancels.  A
+    // chunk of one channel has no partner, and rocFFT transforms row by row.
     void run_am(int first, int cnt, const float2* iq, float* audio, hipStream_t s, bool envelope_ready) {
-        if (!envelope_ready) {
-            StageTimer tm(ST_ENVELOPE, s);
-            launch_envelope(iq, buf_m.as<float>(), (int64_t)cnt * B, s);
+        const bool scaled = pair_scaled(cnt);
+        {
+            std::optional<StageTimer> tm;   // the scaling is timed with the envelope kernel it follows
+            if (!envelope_ready) {
+                tm.emplace(ST_ENVELOPE, s);
+                launch_envelope(iq, buf_m.as<float>(), (int64_t)cnt * B, s);
+            }
+            if (scaled) launch_am_pair_scale(buf_m.as<float>(), B, cnt, buf_scale.as<float>(), s);
         }
         const bool dc = run_real(cnt, audio, s, nullptr, PhaseRows{});
         if (agc_on) {
-            agc_tail(first, cnt, audio, s);
+            agc_tail(first, cnt, audio, s, scaled ? cnt : 0);
             return;
         }
         StageTimer tm(ST_AM_TAIL, s);
         launch_am_tail(audio, A, cnt, dc ? buf_dc.as<float2>() : nullptr, s);
     }
 
-    // USB / LSB (include/rcfm.h): where the sideband's spectrum comes from, for fused_ssb_ifft.
-    SsbSource ssb_source(const float2* X, const int32_t* base32, int64_t N) const {
-        return SsbSource{X, base32, N, B, kind == RCFM_LSB, geom.wr.as<float>(), geom.nyq_bin, geom.nyq_factor};
+    // AM / USB / LSB: does a chunk of cnt channels go through transforms that two channels share?
+    bool pair_scaled(int cnt) const { return cnt > 1 && buf_scale.bytes() != 0; }
+
+    // USB / LSB (include/rcfm.h): where the sideband's spectrum comes from, for fused_ssb_ifft.  The inverse transform
+    // carries Y0 + j Y1 of two channels at their stations' levels: with more than one channel in the chunk the load
+    // multiplies each by its own power of two (pair_scale.h), found here from the bins it will read; the division by
+    // the row's RMS cancels it.
+    SsbSource ssb_source(const float2* X, const int32_t* base32, int64_t N, int cnt, hipStream_t s) const {
+        SsbSource src{X, base32, N, B, kind == RCFM_LSB, geom.wr.as<float>(), geom.nyq_bin, geom.nyq_factor};
+        if (pair_scaled(cnt)) {
+            launch_ssb_pair_scale(X, base32, B, (int)std::min<int64_t>(A / 2, (B - 1) / 2), src.lower, cnt,
+                                  buf_scale.as<float>(), s);
+            src.row_scale = buf_scale.as<float>();
+        }
+        return src;
     }
 
-    void ssb_tail(int first, int cnt, float* audio, hipStream_t s) {
+    void ssb_tail(int first, int cnt, float* audio, hipStream_t s, bool scaled) {
         if (agc_on) {
-            agc_tail(first, cnt, audio, s);
+            agc_tail(first, cnt, audio, s, scaled ? cnt : 0);
             return;
         }
         StageTimer tm(ST_SSB_TAIL, s);
@@ -386,9 +413,9 @@ struct rcfm_demod_s {
         {
             StageTimer tm(ST_IFFT_A, s);
             TILE_CALL(narrow_launch(*eng_A, (cnt + 1) / 2, opt_narrow), fused_ssb_ifft, *eng_A,
-                      ssb_source(t.spectrum(), t.base_dev.as<int32_t>() + first, t.n), audio, buf_TA.as<float2>(), cnt, s);
+                      ssb_source(t.spectrum(), t.base_dev.as<int32_t>() + first, t.n, cnt, s), audio, buf_TA.as<float2>(), cnt, s);
         }
-        ssb_tail(first, cnt, audio, s);
+        ssb_tail(first, cnt, audio, s, pair_scaled(cnt));
     }
 
     // USB / LSB, route 2, from channel samples: FFT_B keeping |k| <= min(A, B) / 2, then the same inverse transform
@@ -404,7 +431,7 @@ struct rcfm_demod_s {
             }
             StageTimer tm(ST_IFFT_A, s);
             TILE_CALL(narrow_launch(*eng_A, (cnt + 1) / 2, opt_narrow), fused_ssb_ifft, *eng_A,
-                      ssb_source(buf_Z.as<float2>(), nullptr, B), audio, buf_TA.as<float2>(), cnt, s);
+                      ssb_source(buf_Z.as<float2>(), nullptr, B, cnt, s), audio, buf_TA.as<float2>(), cnt, s);
         } else {
             size_t need = 0;
             FftPlan& f1 = c2c_fwd_B.get(FftKind::C2C_FORWARD, B, cnt, false, need);
@@ -424,7 +451,7 @@ struct rcfm_demod_s {
             StageTimer tm(ST_IFFT_A, s);
             f2.exec(buf_V.get(), audio, work.get(), s);
         }
-        ssb_tail(first, cnt, audio, s);
+        ssb_tail(first, cnt, audio, s, eng_B && eng_A && pair_scaled(cnt));
     }
 
     // wbfm.py:77-80  FM(B->B) and the pilot band-pass

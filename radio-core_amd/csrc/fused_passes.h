@@ -45,6 +45,9 @@ struct SsbSource {
     bool lower;            // LSB: bin -k, conjugated, in the place of bin +k
     const float* wr;       // Decimate(B -> A)'s folded Hamming weight (ResampleGeom::wr)
     int nyq_bin; float nyq_factor;   // ... and its Nyquist rule (ResampleGeom)
+    // Per-channel power of two (pair_scale.h) that the load multiplies channel c by, so that the two members of a pair
+    // reach their shared transform at comparable scale; nullptr: none.
+    const float* row_scale = nullptr;
 };
 
 // fused_real_pair_fft / StorePruned: keep only bins 0 .. n/2 (all the packed Hilbert chain reads)

@@ -840,6 +840,7 @@ struct LoadSsbPairT {
     const float2* X;
     const int32_t* base;    // DIRECT: per channel (N - roll) mod N
     const float* wr;        // folded Hamming weight, at least kmax + 1 entries
+    const float* row_scale; // per channel 2^e (pair_scale.h), or nullptr
     float two_pi_over_n, delta;
     float c0, c1, c2, c3;   // 0.5 + 0.5 cos(th) = c0 + t c1 + t^2 c2 + t^3 c3, t = th^2
     int B, A, count;
@@ -876,9 +877,12 @@ struct LoadSsbPairT {
             w0s *= fmaf(t, fmaf(t, fmaf(t, c3, c2), c1), c0);
         }
         const float2 w = ssb_weights(w0s, f.kk, kmax, f.mirrored, lower != 0, nyq_bin, nyq_factor);
-        const float w1 = (2 * id.batch + 1 < count) ? 1.f : 0.f;   // an odd last channel rides alone
-        const float2 y0 = make_float2(a.x * w.x, a.y * w.y);
-        const float2 y1 = make_float2(b.x * w.x * w1, b.y * w.y * w1);
+        // each member times its own power of two (exact): a weak channel is not rounded at the scale of its partner
+        const int c0 = 2 * id.batch;
+        const float s0 = row_scale ? row_scale[c0] : 1.f;
+        const float w1 = (c0 + 1 < count) ? (row_scale ? row_scale[c0 + 1] : 1.f) : 0.f;   // an odd last channel rides alone
+        const float2 y0 = make_float2(a.x * (w.x * s0), a.y * (w.y * s0));
+        const float2 y1 = make_float2(b.x * (w.x * w1), b.y * (w.y * w1));
         // Z = Y0 + j Y1, handed on with re / im exchanged: inverse transform by the swap identity
         return make_float2(y0.y + y1.x, y0.x - y1.y);
     }
@@ -895,6 +899,7 @@ void fused_ssb_ifft(const FftEngine& e, const SsbSource& src, float* y, float2* 
         ld.X = src.X;
         ld.base = src.base32;
         ld.wr = src.wr;
+        ld.row_scale = src.row_scale;
         ld.two_pi_over_n = (float)(6.28318530717958647692 / (double)src.N);
         ld.delta = (src.N % 2) ? (float)(3.14159265358979323846 / (double)src.N) : 0.f;
         ld.c0 = 1.f;   // Hann: a0 = 0.5 in LoadTunerGatherFast's series
